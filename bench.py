@@ -9,8 +9,11 @@ A "step" = one pass of that path over one batch of `--scenes-per-gpu` synthetic 
 --gpus N`, WORLD_SIZE set) this process IS one of the ranks; started plainly (`python bench.py --gpus N`, no WORLD_SIZE) it launches the N
 ranks itself -- like a plain `python -m src.main` under Lightning (src/main.py:104-116) -- and every rank asserts world size == --gpus.
 Scenes are independent: they are sharded over ranks with NO data-path collective ("scaling": "weak").
-Prints ONE JSON line (rank 0) with `roofline` (dominant hand-written kernel, measured with HIP events on the launch
-stream in an extra instrumented step) and `cpu_baseline` (the CPU oracle timed on the host cores, N=1 only).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the line; `--dump-outputs DIR` also writes
+what the last timed step computed (see dump_outputs).  `--full` adds everything else the line can carry: `roofline` (dominant
+hand-written kernel, measured with HIP events on the launch stream in an extra instrumented step), `cpu_baseline` (the CPU oracle timed on
+the host cores, N=1 only), the render PSNR against the oracle chain, the f16 / f32 precision legs, the 70-view demo workload, the
+single-scene latency and the training step (`--mode both`).  Without `--full` those keys are null.
 """
 from __future__ import annotations
 
@@ -28,6 +31,7 @@ if ROOT not in sys.path:
 
 PEAK_MFMA_16BIT_TFLOPS = 2500.0  # dense bf16/f16 MFMA, MI355X_MICROARCH.md
 PEAK_HBM_GBS = 8000.0
+DUMP_SAMPLE = 1 << 18        # --dump-outputs: elements kept of a larger output (a fixed seeded sample)
 DTYPE_NOTE = {"split": "f32 (f32 activations; products as 3 x f16 MFMA on hi+lo operand pairs, f32 accumulate)", "f16": "f16", "bf16": "bf16",
               "f32": "f32 (exact-f32 MFMA)"}
 
@@ -43,9 +47,15 @@ def parse():
     ap.add_argument("--dtype", default="split", choices=["split", "f16", "bf16", "f32"],
                     help="operand class of the headline: split (default) = f32 activations, f16 hi+lo operands, three MFMAs per product -- the "
                          "precision that meets the render tolerance; f16 / bf16 = the fast TF32-class path; f32 = exact-f32 MFMA")
-    ap.add_argument("--mode", default="both", choices=["infer", "train", "both"],
-                    help="infer: the headline forward metric only; both (default): also time the full training step (BASELINE config 4/5) "
-                         "and report it in the `train` object of the same JSON line; train: `value` IS the training throughput")
+    ap.add_argument("--mode", default=None, choices=["infer", "train", "both"],
+                    help="infer (default): the headline forward metric only; both (default with --full): also time the full training step "
+                         "(BASELINE config 4/5) and report it in the `train` object of the same JSON line; train: `value` IS the training throughput")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement after the headline: roofline step, CPU baseline and render PSNR vs the oracle, "
+                         "f16 / f32 precision legs, 70-view demo workload, single-scene latency, training legs (--mode defaults to both)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32; arrays larger than "
+                         f"{DUMP_SAMPLE} elements as a fixed seeded sample of that many elements)")
     ap.add_argument("--train-scenes-per-gpu", type=int, default=24)    # README.md:104 / distill.yaml: 24 scenes per GPU
     ap.add_argument("--train-steps", type=int, default=3)
     ap.add_argument("--train-split-scenes", type=int, default=8, help="scenes per GPU of the reference-precision (split class) training leg: f32 "
@@ -64,7 +74,36 @@ def parse():
                     help="no GPU work: run the N > 1 control flow of this file (process-group init from the launcher's environment, barriers, MAX-reduce of "
                          "the elapsed time, the training leg's watchdog and one GradReducer exchange) on CPU with the gloo backend and print the JSON line")
     ap.add_argument("--leg-steps", type=int, default=10, help="timed steps of the secondary precision legs")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.mode is None:
+        args.mode = "both" if args.full else "infer"
+    if args.dump_outputs and args.mode == "train":
+        ap.error("--dump-outputs writes the outputs of the inference step; --mode train does not time it")
+    return args
+
+
+def dump_outputs(dirname, out, r):
+    """--dump-outputs: what a caller of the timed step receives from its last execution -- every tensor of the encoder's output dict, the
+    fields of its Gaussians, the rendered target views' color and depth -- as DIR/<name>.npy, float32 (float64 stays float64).  An array of
+    more than DUMP_SAMPLE elements is written as DUMP_SAMPLE of its elements in row-major order, at flat indices drawn without replacement
+    by a generator seeded with the array's name and size: the same for every run with the same arguments, so two builds compare file by file."""
+    import zlib
+
+    import numpy as np
+    arrays = {}
+    named = [("gaussians_" + k, v) for k, v in vars(out["gaussians"]).items()] + [(k, v) for k, v in out.items() if k != "gaussians"]
+    for name, t in named + [("color", r.color), ("depth", r.depth)]:
+        if torch.is_tensor(t) and not any(t is a for a in arrays.values()):      # (gaussian_centers IS gaussians.means)
+            arrays[name] = t
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            rng = np.random.default_rng([zlib.crc32(name.encode()), t.numel()])
+            flat = np.sort(rng.choice(t.numel(), size=DUMP_SAMPLE, replace=False))
+            t = t[tuple(torch.from_numpy(i).to(t.device) for i in np.unravel_index(flat, tuple(t.shape)))]
+        a = t.cpu().numpy().astype(np.float64 if t.dtype == torch.float64 else np.float32)
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def _auto_blocks(B, dt, dev):
@@ -447,8 +486,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    last = step()                            # (held past the loop only: what --dump-outputs writes)
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
@@ -461,9 +501,12 @@ def main():
     value = world * B * args.steps / elapsed
     if cap["flags"] and bool(torch.stack(cap["flags"]).max().item() != 0):
         raise RuntimeError("a timed rasterizer call outgrew its instance capacity (it rendered background only): the measurement is invalid")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, *last)
+    del last
 
     roofline, extra = None, {}
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         kt = KernelTimer()
         P = V * 256 * 256
 
@@ -581,7 +624,7 @@ def main():
     cpu_baseline = None
     psnr_vs_oracle = None
     psnr_ctx = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # ---- CPU baseline leg: the oracle (a restatement of the reference, "port"), timed on the host cores ----
         from oracle import encoder_ref as er
         from oracle import raster_ref as rr
@@ -734,7 +777,7 @@ def main():
             torch.cuda.empty_cache()
 
     targets70 = None
-    if rank == 0 and world == 1 and args.mode != "train" and not args.no_targets70:
+    if rank == 0 and world == 1 and args.full and args.mode != "train" and not args.no_targets70:
         targets70 = targets70_leg()
 
     # ---- single-scene latency: the reference's ONLY published number for this path is "~0.1 s" per scene end to end
@@ -797,11 +840,11 @@ def main():
             torch.cuda.empty_cache()
 
     latency_b1 = None
-    if rank == 0 and world == 1 and args.mode != "train" and not args.no_latency:
+    if rank == 0 and world == 1 and args.full and args.mode != "train" and not args.no_latency:
         latency_b1 = latency_leg()
 
     f32_path = fast_path = None
-    if rank == 0 and world == 1 and args.mode != "train":
+    if rank == 0 and world == 1 and args.full and args.mode != "train":
         if not args.no_fast and args.dtype not in ("f16", "bf16"):
             fast_path = precision_leg("f16", PEAK_MFMA_16BIT_TFLOPS, 1.0)
         if not args.no_f32 and args.dtype != "f32":

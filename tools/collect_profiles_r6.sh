@@ -7,8 +7,8 @@ O=$R/gpurun_out/p6
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 B="python $R/bench.py --mode infer --no-cpu-baseline --no-f32 --no-fast --no-targets70 --no-latency"
-if [[ $parts == *line* ]]; then      # the full default bench line of this build (what the driver runs)
-  python $R/bench.py > $O/bench_line.json 2> $O/bench_line.err
+if [[ $parts == *line* ]]; then      # the full bench line of this build (every leg: --full)
+  python $R/bench.py --full > $O/bench_line.json 2> $O/bench_line.err
 fi
 if [[ $parts == *infer* ]]; then     # per-kernel time of the default (split) inference step, 5 executed steps
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- $B --no-roofline --steps 4 --warmup 1 > $O/stats.log 2>&1

@@ -10,4 +10,4 @@ rm -rf $O/stats
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- $B --no-roofline --steps 4 --warmup 1 > $O/stats.log 2>&1
 find $O -name "*kernel_trace.csv" -size +8M -delete
 find $O -name "*.db" -delete
-cd $R && python bench.py > $O/bench_full.log 2>&1; tail -1 $O/bench_full.log > $O/bench_line.json
+cd $R && python bench.py --full > $O/bench_full.log 2>&1; tail -1 $O/bench_full.log > $O/bench_line.json
