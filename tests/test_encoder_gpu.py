@@ -183,7 +183,8 @@ def test_deterministic_mode_is_bit_reproducible(monkeypatch):
     24-scene step, nothing at B = 1): (i) two runs of the full ViT-L split forward are torch.equal in every output; (ii) the rasterizer's
     instance count and image repeat exactly.  NOT guaranteed, and bounded here instead: scene 0 alone vs scene 0 inside a batch of 3 --
     the kernel a row is routed to (tile shape, LayerNorm / attention variant) depends on the batch's row count and the variants sum in
-    different orders (forcing one GEMM tile shape alone, VS_GEMM_MI=4, does not remove it: tools/batch_invariance3.py); replicas of EQUAL
+    different orders (forcing one GEMM tile shape alone -- a since-retired switch that pinned the 128 x 128 tiles -- was measured not to remove
+    it: tools/batch_invariance3.py at 8054b70); replicas of EQUAL
     shards, which is what scene sharding produces, take identical routes."""
     from vicasplat_amd.model.decoder.cuda_splatting import render_cuda
     from vicasplat_amd import raster

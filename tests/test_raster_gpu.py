@@ -360,10 +360,13 @@ def _close(a, b, name, rtol):
 
 @pytest.fixture(params=["0", "4"])
 def rbwd_waves(request, monkeypatch):
-    """Both render-backward routes (round 6; VS_RBWD_WAVES is read per call): 0 = the default of every differentiated call -- the
-    segment-parallel replay from the forward's blending checkpoints (front to back, a wave per 512-entry segment, atomics-free staging);
-    4 = the whole-list kernel a caller without VS_RASTER_SAVE_FOR_BACKWARD gets (four waves per tile, back to front from final_T)."""
-    monkeypatch.setenv("VS_RBWD_WAVES", request.param)
+    """Both render-backward routes (round 6; the backward picks one by the presence of the forward's checkpoints): 0 = the default of every
+    differentiated call -- the segment-parallel replay from the forward's blending checkpoints (front to back, a wave per 512-entry segment,
+    atomics-free staging); 4 = the whole-list kernel a caller without VS_RASTER_SAVE_FOR_BACKWARD gets (four waves per tile, back to front from
+    final_T), reached as that caller does: the flag _Rasterize.forward ORs in is 0, so the forward stores no VS_BUF_CHECKPOINT."""
+    if request.param == "4":
+        from vicasplat_amd import _lib
+        monkeypatch.setattr(_lib, "VS_RASTER_SAVE_FOR_BACKWARD", 0)
     return request.param
 
 

@@ -1,5 +1,5 @@
 #!/bin/bash
-# SQ counters of the split attention kernel (attention_sp_kernel, or attention_split_kernel with VS_ATTN_PACKED=0) on one shape: bash tools/pmc_one_attn.sh <tag> encoder|video
+# SQ counters of the split attention kernel on packed q | k | v (attention_sp_kernel) on one shape: bash tools/pmc_one_attn.sh <tag> encoder|video
 R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out/pa_$1
 mkdir -p $O

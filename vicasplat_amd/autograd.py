@@ -9,7 +9,6 @@ scaled-dot-product attention and nn.Conv2d(k=3, s=1, p=1) on that path.
 """
 from __future__ import annotations
 
-import os
 from typing import Optional
 
 import torch
@@ -197,14 +196,11 @@ class LinearFn(torch.autograd.Function):
         return (None if dx is None else dx.view(xshape).to(xdtype)), dw, db, None, None
 
 
-_MLP_DGELU_EPI = os.environ.get("VS_MLP_DGELU_EPI", "1") != "0"      # A/B switch: 0 = GELU and its backward as separate nodes in the split class too
-
-
 def linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], dt: torch.dtype, rope=None, scale_sources=(), gelu_in: bool = False) -> torch.Tensor:
     """nn.Linear in the operand dtype `dt`.  K must be a multiple of 64 for the MFMA kernels; tiny odd shapes (the 9 -> C
     intrinsic embedding) stay on torch in f32.  gelu_in: y = gelu(x) @ w^T + b (croco/blocks.py:60-72: fc2(act(fc1(x)))) -- in the split class ONE
     node whose backward multiplies by GELU'(x) in the dX GEMM's epilogue."""
-    if gelu_in and not (dt == SPLIT and _MLP_DGELU_EPI and rope is None):
+    if gelu_in and not (dt == SPLIT and rope is None):
         x, gelu_in = gelu(x), False
     if dt == SPLIT:
         return LinearSplitFn.apply(x, w, b, rope, tuple(scale_sources), gelu_in)
@@ -474,9 +470,6 @@ class LayerNormModFn(torch.autograd.Function):
         return dx, dw, db, (dsc if has_mod else None), (dsh if has_mod else None), None, None, None, dlead, None, None
 
 
-_LN_SKIP = os.environ.get("VS_LN_SKIP_FUSED", "1") != "0"       # A/B switch: 0 = the residual gradient meets the LayerNorm's in an autograd add pass
-
-
 def layernorm_mod(x, w, b, *, scale=None, shift=None, mod_rows=0, out_dtype=torch.float16, eps=1e-6, lead=None, lead_rows=0, skip=False):
     """x [..., C] (any leading dims; scale/shift [G, C] apply to consecutive groups of mod_rows rows).  With `lead` the result is
     2-D [rows + rows // lead_rows, C] (see LayerNormModFn).  skip=True (x 2-D): returns (LN(x), x') with x' = x routed through the node -- use x' as
@@ -484,8 +477,6 @@ def layernorm_mod(x, w, b, *, scale=None, shift=None, mod_rows=0, out_dtype=torc
     lead_shape = x.shape[:-1]
     if skip:
         assert x.dim() == 2
-        if not _LN_SKIP:
-            return layernorm_mod(x, w, b, scale=scale, shift=shift, mod_rows=mod_rows, out_dtype=out_dtype, eps=eps, lead=lead, lead_rows=lead_rows), x
         return LayerNormModFn.apply(x, w, b, scale, shift, mod_rows, out_dtype, eps, lead, lead_rows, True)
     y = LayerNormModFn.apply(x.reshape(-1, x.shape[-1]), w, b, scale, shift, mod_rows, out_dtype, eps, lead, lead_rows)
     return y if lead is not None else y.view(*lead_shape, x.shape[-1])

@@ -12,8 +12,6 @@
 // (means [P,3], covariances [P,3,3], harmonics [P,3,d_sh], opacities [P], scales [P,3], rotations [P,4], raw [P,11+3*d_sh]).
 #include "common.h"
 
-#include <cstdlib>
-
 #include <type_traits>
 
 namespace {
@@ -476,8 +474,7 @@ extern "C" int vs_gaussian_adapter(const void *pts, int64_t pts_pix, int64_t pts
                          ((64 * pts_pix) % ev == 0) && ((64 * gs_pix) % ev == 0);
     if (dense16) {
         dim3 g64((unsigned)vs::cdiv64(npix, 64));
-        static const int npx = [] { const char *e = getenv("VS_ADAPTER_NPX"); return e ? atoi(e) : 32; }();
-        if (in_dtype == 0 && npx == 32 && ((32 * pts_pix) % ev == 0) && ((32 * gs_pix) % ev == 0))
+        if (in_dtype == 0 && ((32 * pts_pix) % ev == 0) && ((32 * gs_pix) % ev == 0))
             hipLaunchKernelGGL((adapter_nhwc16_kernel<0, 32>), dim3((unsigned)vs::cdiv64(npix, 32)), dim3(64), 0, stream, a);
         else if (in_dtype == 0) hipLaunchKernelGGL(adapter_nhwc16_kernel<0>, g64, dim3(64), 0, stream, a);
         else if (in_dtype == 1) hipLaunchKernelGGL(adapter_nhwc16_kernel<1>, g64, dim3(64), 0, stream, a);

@@ -17,8 +17,6 @@
 // the A-operand layout of the P.V MFMA (keys permuted consistently on the V side).
 #include "common.h"
 
-#include <cstdlib>
-
 namespace {
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
@@ -208,8 +206,9 @@ __device__ __forceinline__ void store_o_rows(const f4 (&o)[4], float l, int q, i
     }
 }
 
-template <bool BF16, int QG, int WPE>
-__global__ void __launch_bounds__(256, WPE) attention_kernel(const AttnArgs a) {
+// occupancy target (waves per EU): 3 for 128-query workgroups, 4 for 64-query ones
+template <bool BF16, int QG>
+__global__ void __launch_bounds__(256, QG == 2 ? 3 : 4) attention_kernel(const AttnArgs a) {
     constexpr int QBLK = 64 * QG;
     __shared__ __attribute__((aligned(16))) unsigned short sK2[2][KB * KROW];   // two-tile ring: one barrier per tile
     __shared__ __attribute__((aligned(16))) unsigned short sV2[2][KB * KROW];    // row-major, read through ds_read_b64_tr_b16
@@ -500,7 +499,6 @@ struct AttnArgsSplit {
     float scale_log2e;
     float *lse;
     int out_packed;   // write O in the packed (hi, lo) form of the split class (the A operand of the projection GEMM: vs_gemm_split_packed)
-    int xcd;          // 1: XCD-aware (tile, head, batch) ids: the query tiles of one (batch, head) read its K / V behind ONE L2 (attention_bwd.hip block_bhx)
 };
 
 // four consecutive columns n .. n + 3 of an f32 row written in the packed (hi, lo) layout of vs_split_pack_weight (gemm_common.h, store_split4)
@@ -549,8 +547,10 @@ __global__ void __launch_bounds__(256, 2) attention_split_kernel(const AttnArgsS
     __shared__ int s_maxlen;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int g = lane >> 4, c16 = lane & 15;
-    int b = blockIdx.z, h = blockIdx.y, bx_ = blockIdx.x;
-    if (a.xcd) {      // consecutive workgroups are dealt to consecutive XCDs: make consecutive LOGICAL ids share one (gemm256_kernel's remap)
+    // XCD-aware (tile, head, batch) ids: consecutive workgroups are dealt to consecutive XCDs, so make consecutive LOGICAL ids share one
+    // (gemm256_kernel's remap): the query tiles of one (batch, head) read its K / V behind ONE L2 (attention_bwd.hip block_bhx)
+    int b, h, bx_;
+    {
         const int gx = gridDim.x, gy = gridDim.y, n = gx * gy * gridDim.z;
         const int lin = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
         const int q_ = n >> 3, r_ = n & 7, xc = lin & 7, idx = lin >> 3;
@@ -770,7 +770,7 @@ __device__ __forceinline__ void glds16_sp(const void *gp, unsigned lds_off) {   
 //     tile, so the rescale factor is uniform too and the cross-lane row sum can wait for the end of the kernel (one rows_sum per query
 //     group instead of one per tile);
 //   * MASKED = false: every score is finite, the running maximum is finite after the first tile: no -inf guard.
-template <bool MASKED, bool PLO = true>
+template <bool MASKED>
 __device__ __forceinline__ void softmax_half(f4 (&st)[2], float scale_log2e, float &m_run, float &l_run, f4 (&o)[4], uint4 &pf) {
     float mx = fmaxf(fmaxf(st[0][0], st[0][1]), st[0][2]);
     mx = fmaxf(fmaxf(mx, st[0][3]), st[1][0]);
@@ -799,7 +799,7 @@ __device__ __forceinline__ void softmax_half(f4 (&st)[2], float scale_log2e, flo
         for (int db = 0; db < 4; ++db) o[db] *= alpha;
         m_run = m_new;
     }
-    if constexpr (PLO) l_run += acc.x + acc.y;
+    l_run += acc.x + acc.y;
     // COMPILER-VISIBLE converts: pf feeds the P V MFMAs, and the VALU-write -> MFMA-read wait states come from the compiler's hazard
     // recogniser, which does not look inside inline asm (pack2<> is asm: with it the third query group's rows came out 5e-5 off whenever the
     // scheduler placed its first P V MFMA right behind the convert -- the bug class of gemm_common.h split8 / relu_f32_lds, met again here)
@@ -809,22 +809,13 @@ __device__ __forceinline__ void softmax_half(f4 (&st)[2], float scale_log2e, flo
     pf.y = __builtin_bit_cast(unsigned, __builtin_convertvector(f2s_{st[0][2], st[0][3]}, h2s_));
     pf.z = __builtin_bit_cast(unsigned, __builtin_convertvector(f2s_{st[1][0], st[1][1]}, h2s_));
     pf.w = __builtin_bit_cast(unsigned, __builtin_convertvector(f2s_{st[1][2], st[1][3]}, h2s_));
-    if constexpr (!PLO) {
-        // P as one f16: the row sum is taken over the ROUNDED weights the P V product uses, so the output is an exact weighted mean of V
-        // under weights p (1 + e), |e| <= 2^-11 -- the rounding no longer shifts the mean, only the spread around it
-        const h2s_ one2 = h2s_{(_Float16)1.0f, (_Float16)1.0f};
-        float a2 = __builtin_amdgcn_fdot2(__builtin_bit_cast(h2s_, pf.x), one2, 0.f, false);
-        a2 = __builtin_amdgcn_fdot2(__builtin_bit_cast(h2s_, pf.y), one2, a2, false);
-        a2 = __builtin_amdgcn_fdot2(__builtin_bit_cast(h2s_, pf.z), one2, a2, false);
-        l_run += __builtin_amdgcn_fdot2(__builtin_bit_cast(h2s_, pf.w), one2, a2, false);
-    }
 }
 
 // One tile of one wave: its 32 keys (rows kw .. kw + 31 of the staged tile) against its 64 queries.  Straight-line code: ALLQ (all four
 // query groups hold real queries) and MASKED (some query of the wave does not see all 32 keys) are compile-time, so the 96 MFMAs, the four
 // softmax steps and the 24 LDS reads of a tile form ONE basic block the scheduler can interleave.  kofs / vofs: per-lane byte offsets inside a
 // K / V tile (swizzle applied), loop invariant; the ring slot is a compile-time constant, so every LDS address is register + immediate.
-template <int NG, bool ALLQ, bool MASKED, bool PLO>
+template <int NG, bool ALLQ, bool MASKED>
 __device__ __forceinline__ void sp_tile(const unsigned char *sK, const unsigned char *sV, const int (&kofs)[2][2], const int (&vofs)[8], int nact,
                                         const int (&my_len)[NG], int kbase, int g, float scale_log2e, const uint4 (&qfh)[NG][2], const uint4 (&qfl)[NG][2],
                                         float (&m_run)[NG], float (&l_run)[NG], f4 (&o)[NG][4]) {
@@ -854,11 +845,11 @@ __device__ __forceinline__ void sp_tile(const unsigned char *sK, const unsigned 
                 for (int r = 0; r < 4; ++r)
                     if (nb * 16 + r >= lim) st[u][nb][r] = -INFINITY;
         }
-        softmax_half<MASKED, PLO>(st[u], scale_log2e, m_run[u], l_run[u], o[u], pfh[u]);     // st now holds P (f32), pfh its rne16
+        softmax_half<MASKED>(st[u], scale_log2e, m_run[u], l_run[u], o[u], pfh[u]);     // st now holds P (f32), pfh its rne16
         const unsigned hh[4] = {pfh[u].x, pfh[u].y, pfh[u].z, pfh[u].w};
         unsigned ll[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
-        for (int w = 0; w < (PLO ? 4 : 0); ++w) {
+        for (int w = 0; w < 4; ++w) {
             // lo = rne16(p - float(hi)): the difference on v_fma_mix_f32 (f16 source operand, exact f32 result: one instruction instead of a
             // convert and a subtract), the rounding on a COMPILER-VISIBLE convert -- the value that feeds the P V MFMAs must come out of an
             // instruction the hazard recogniser sees (VALU write -> MFMA read wait states); asm -> VALU needs no software wait
@@ -885,18 +876,11 @@ __device__ __forceinline__ void sp_tile(const unsigned char *sK, const unsigned 
         const uint4 vh = make_uint4(h0.x, h0.y, h1.x, h1.y), vl = make_uint4(l0.x, l0.y, l1.x, l1.y);
 #pragma unroll
         for (int u = 0; u < NG; ++u)
-            if (ALLQ || u < nact) {
-                if constexpr (PLO) {
-                    o[u][db] = mma3(vh, vl, pfh[u], pfl[u], o[u][db]);
-                } else {      // P as ONE f16 (p in [0, 1]: its lo half carries <= 2^-12 p): V_lo P_hi + V_hi P_hi, two MFMAs instead of three
-                    o[u][db] = mfma<false>(vl, pfh[u], o[u][db]);
-                    o[u][db] = mfma<false>(vh, pfh[u], o[u][db]);
-                }
-            }
+            if (ALLQ || u < nact) o[u][db] = mma3(vh, vl, pfh[u], pfl[u], o[u][db]);
     }
 }
 
-template <int NG, bool PLO = true>
+template <int NG>
 __global__ void __launch_bounds__(256, 2) attention_sp_kernel(const AttnArgsSP a) {
     constexpr int QW = 16 * NG;                                               // queries per wave (NG MFMA groups of 16), 2 * QW per workgroup
     constexpr int TILE_B = KB * 256;                                          // one K (or V) tile: 64 keys x 256 bytes
@@ -1035,10 +1019,10 @@ __global__ void __launch_bounds__(256, 2) attention_sp_kernel(const AttnArgsSP a
         if (kb >= wave_len) return;                          // none of this wave's queries sees any of its keys of this tile
         const bool masked = kb + 32 > wave_min;              // (wave-uniform)
         if (allq) {
-            if (masked) sp_tile<NG, true, true, PLO>(sK, sV, kofs, vofs, nact, my_len, kb, g, a.scale_log2e, qfh, qfl, m_run, l_run, o);
-            else sp_tile<NG, true, false, PLO>(sK, sV, kofs, vofs, nact, my_len, kb, g, a.scale_log2e, qfh, qfl, m_run, l_run, o);
+            if (masked) sp_tile<NG, true, true>(sK, sV, kofs, vofs, nact, my_len, kb, g, a.scale_log2e, qfh, qfl, m_run, l_run, o);
+            else sp_tile<NG, true, false>(sK, sV, kofs, vofs, nact, my_len, kb, g, a.scale_log2e, qfh, qfl, m_run, l_run, o);
         } else {
-            sp_tile<NG, false, true, PLO>(sK, sV, kofs, vofs, nact, my_len, kb, g, a.scale_log2e, qfh, qfl, m_run, l_run, o);
+            sp_tile<NG, false, true>(sK, sV, kofs, vofs, nact, my_len, kb, g, a.scale_log2e, qfh, qfl, m_run, l_run, o);
         }
     };
     for (int kt = 0; kt < maxlen; kt += 2 * KB) {            // two tiles per trip: the ring slot is a compile-time constant
@@ -1102,7 +1086,7 @@ __global__ void __launch_bounds__(256, 2) attention_sp_kernel(const AttnArgsSP a
 //  tile: correct (4.8e-7 of float64), and 386 vs 392 us on the frame encoder's shape, 415 vs 408 on the cross-neighbour shape: nothing.  A
 //  workgroup of these shapes spends ~2 us of its ~21 us in MFMAs; the rest is the dependent chain Q load -> first DMA -> barrier -> ...
 //  -> merge -> store at 8 waves per CU, which a shorter key loop does not shorten.
-//  Also measured, kept as an OPT-IN switch (VS_ATTN_PLO=0): P as ONE f16 in the P V product -- two MFMAs instead of three, no lo split --
+//  Also measured and not kept (an opt-in switch until 8054b70): P as ONE f16 in the P V product -- two MFMAs instead of three, no lo split --
 //  with the row sum taken over the ROUNDED weights (v_dot2_f32_f16 against ones), so that the output stays an exact weighted mean of V under
 //  weights p (1 + e), |e| <= 2^-11: 25.95 -> 22.95 ms per step.  With that normalisation the whole encoder moves from <= 1.3e-5 to <= 2.5e-5
 //  of the reference's f64 goldens (bar 2e-4), the render PSNR against the oracle chain from 73-79 to 71.5-73.7 dB, the poses from 1.4e-6 to
@@ -1297,29 +1281,21 @@ extern "C" int vs_attention_lse(const void *q, const void *k, const void *v, voi
                      "vs_attention: packed q | k | v need row strides that are multiples of 32 (4-byte units) and 128-byte aligned head-0 columns");
             AttnArgsSP f;
             f.q = (const unsigned char *)q; f.k = (const unsigned char *)k; f.v = (const unsigned char *)v; f.out = (float *)out; f.kv_seg = kv_seg; f.q_kvlen = q_kvlen;
-            static const int ng = [] { const char *e = getenv("VS_ATTN_SP_NG"); return e ? atoi(e) : 3; }();
-            f.nbatch = nbatch; f.H = H; f.Lq = Lq; f.Lk = Lk; f.nqt = vs::cdiv(Lq, 32 * ng); f.q_batch_rows = q_batch_rows; f.k_batch_rows = k_batch_rows;
+            f.nbatch = nbatch; f.H = H; f.Lq = Lq; f.Lk = Lk; f.nqt = vs::cdiv(Lq, 32 * 3); f.q_batch_rows = q_batch_rows; f.k_batch_rows = k_batch_rows;
             f.ldq_b = 4LL * ldq; f.ldk_b = 4LL * ldk; f.ldv_b = 4LL * ldv; f.ldo = ldo; f.scale_log2e = scale * 1.4426950408889634f; f.lse = lse;
             f.out_packed = out_packed;
             const long long nwg = (long long)f.nqt * H * nbatch;
             VS_CHECK(nwg < (1LL << 31), "vs_attention: grid too large");
-            static const int plo = [] { const char *e = getenv("VS_ATTN_PLO"); return e ? atoi(e) : 1; }();
-            if (ng == 4) hipLaunchKernelGGL(attention_sp_kernel<4>, dim3((unsigned)nwg), dim3(256), 0, stream, f);
-            else if (ng == 2) hipLaunchKernelGGL(attention_sp_kernel<2>, dim3((unsigned)nwg), dim3(256), 0, stream, f);
-            else if (plo == 0 || (plo == 2 && q_kvlen) || (plo == 3 && !q_kvlen)) hipLaunchKernelGGL((attention_sp_kernel<3, false>), dim3((unsigned)nwg), dim3(256), 0, stream, f);
-            else hipLaunchKernelGGL(attention_sp_kernel<3>, dim3((unsigned)nwg), dim3(256), 0, stream, f);
+            hipLaunchKernelGGL(attention_sp_kernel<3>, dim3((unsigned)nwg), dim3(256), 0, stream, f);
             VS_HIP(hipGetLastError());
             return 0;
         }
         AttnArgsSplit f;
-        { static const int x_ = [] { const char *e = getenv("VS_ATTN_SPLIT_XCD"); return e ? atoi(e) : 1; }(); f.xcd = x_; }
         f.q = (const float *)q; f.k = (const float *)k; f.v = (const float *)v; f.out = (float *)out; f.kv_seg = kv_seg; f.q_kvlen = q_kvlen;
         f.nbatch = nbatch; f.H = H; f.Lq = Lq; f.Lk = Lk; f.q_batch_rows = q_batch_rows; f.k_batch_rows = k_batch_rows;
         f.ldq = ldq; f.ldk = ldk; f.ldv = ldv; f.ldo = ldo; f.scale_log2e = scale * 1.4426950408889634f; f.lse = lse; f.out_packed = out_packed;
         const int Lk_eff = kv_seg ? 2 * Lk : Lk;
-        static const int force_qg4 = [] { const char *e = getenv("VS_ATTN_SPLIT_QG"); return e ? atoi(e) : 0; }();
-        bool big = (long long)vs::cdiv(Lq, 128) * H * nbatch >= 512 && Lk_eff > 256;
-        if (force_qg4) big = force_qg4 == 2;
+        const bool big = (long long)vs::cdiv(Lq, 128) * H * nbatch >= 512 && Lk_eff > 256;
         if (big) hipLaunchKernelGGL((attention_split_kernel<2>), dim3(vs::cdiv(Lq, 128), H, nbatch), dim3(256), 0, stream, f);
         else hipLaunchKernelGGL((attention_split_kernel<1>), dim3(vs::cdiv(Lq, 64), H, nbatch), dim3(256), 0, stream, f);
         VS_HIP(hipGetLastError());
@@ -1342,10 +1318,7 @@ extern "C" int vs_attention_lse(const void *q, const void *k, const void *v, voi
     a.scale_log2e = scale * 1.4426950408889634f;
     a.lse = lse;
     // 128 queries per workgroup when that still leaves >= 2 workgroups per CU; else 64
-    static const int force_qg = [] { const char *e = getenv("VS_ATTN_QG"); return e ? atoi(e) : 0; }();
-    static const int force_wpe = [] { const char *e = getenv("VS_ATTN_WPE"); return e ? atoi(e) : 0; }();
-    static const int force_res = [] { const char *e = getenv("VS_ATTN_RES"); return e ? atoi(e) : -1; }();
-    if (!kv_seg && !q_kvlen && Lk <= kResMaxKeys && Lq <= 3 * 8 * 16 && force_res != 0) {
+    if (!kv_seg && !q_kvlen && Lk <= kResMaxKeys && Lq <= 3 * 8 * 16) {
         const int Lkp = (Lk + 15) & ~15;
         const size_t lds = (size_t)(2 * Lkp * KROW) * sizeof(unsigned short);   // K and V, row-major
         dim3 grid(1, H, nbatch);
@@ -1362,20 +1335,16 @@ extern "C" int vs_attention_lse(const void *q, const void *k, const void *v, voi
     // 128 queries per workgroup only for long key sequences (more MFMAs per staged tile); the 257/516-key shapes are
     // latency bound and run faster with 64-query workgroups at higher occupancy
     const int Lk_eff = kv_seg ? 2 * Lk : Lk;
-    bool big = (long long)vs::cdiv(Lq, 128) * H * nbatch >= 512 && Lk_eff > 1024;
-    if (force_qg) big = force_qg == 2;
+    const bool big = (long long)vs::cdiv(Lq, 128) * H * nbatch >= 512 && Lk_eff > 1024;
     dim3 block(256);
-#define VS_LAUNCH(QG_, WPE_)                                                                                   \
+#define VS_LAUNCH(QG_)                                                                                         \
     {                                                                                                          \
         dim3 grid(vs::cdiv(Lq, 64 * QG_), H, nbatch);                                                          \
-        if (dtype == 2) hipLaunchKernelGGL((attention_kernel<true, QG_, WPE_>), grid, block, 0, stream, a);    \
-        else hipLaunchKernelGGL((attention_kernel<false, QG_, WPE_>), grid, block, 0, stream, a);              \
+        if (dtype == 2) hipLaunchKernelGGL((attention_kernel<true, QG_>), grid, block, 0, stream, a);          \
+        else hipLaunchKernelGGL((attention_kernel<false, QG_>), grid, block, 0, stream, a);                    \
     }
-    if (big) {
-        if (force_wpe == 2) VS_LAUNCH(2, 2) else VS_LAUNCH(2, 3)
-    } else {
-        if (force_wpe == 2) VS_LAUNCH(1, 2) else VS_LAUNCH(1, 4)
-    }
+    if (big) VS_LAUNCH(2)
+    else VS_LAUNCH(1)
 #undef VS_LAUNCH
     VS_HIP(hipGetLastError());
     return 0;

@@ -13,8 +13,6 @@
 // S and dP are recomputed in both kernels (7 instead of 5 MFMA products per (i, j) tile, no atomics on dQ).
 #include "common.h"
 
-#include <cstdlib>
-
 namespace {
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
@@ -46,14 +44,12 @@ struct AttnBwdArgs {
     const float *o32, *dout32;
     float *dq32;
     int ldo32, lddo32, lddq32, kv_direct;
-    int xcd;     // 1: XCD-aware block ids (block_bhx): the tiles of one (batch, head) run behind ONE L2
 };
 
 // (tile, head, batch) of this workgroup.  The hardware deals consecutive workgroups (x fastest) to consecutive XCDs, which puts the tiles of one
 // (batch, head) -- they all read that head's whole K / V (dq kernels) or Q / dO (dk|dv kernels) -- behind eight different L2s (counters: 76 GB
-// fetched per 8-scene split training step for ~38 GB of operands).  With a.xcd consecutive LOGICAL ids share an XCD (gemm256_kernel's remap).
-__device__ __forceinline__ void block_bhx(const AttnBwdArgs &a, int &b, int &h, int &x) {
-    if (!a.xcd) { b = blockIdx.z; h = blockIdx.y; x = blockIdx.x; return; }
+// fetched per 8-scene split training step for ~38 GB of operands).  So consecutive LOGICAL ids share an XCD (gemm256_kernel's remap).
+__device__ __forceinline__ void block_bhx(int &b, int &h, int &x) {
     const int gx = gridDim.x, gy = gridDim.y, n = gx * gy * gridDim.z;
     const int lin = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
     const int q = n >> 3, r = n & 7, xc = lin & 7, idx = lin >> 3;
@@ -173,7 +169,7 @@ __device__ __forceinline__ void dma_tile(const unsigned short *src, int ld, int 
 // ---- dQ: workgroup = 64 * NG queries (4 waves x NG groups of 16; group u of wave w = rows q0 + (4u + w) * 16 ..), lane = (query c16, key
 // group g); loops over 64-key tiles.  NG = 2 (round 4): a K / V fragment read from LDS feeds the MFMAs of BOTH query groups -- with one group
 // per wave a tile costs a wave 24 LDS fragment reads for 24 MFMAs and the kernel was bound by the LDS pipe, not by the matrix pipe.  A
-// group whose 16 rows lie beyond Lq is skipped (wave-uniform); VS_ATTN_BWD_NG=1 restores one group per wave. ----
+// group whose 16 rows lie beyond Lq is skipped (wave-uniform). ----
 template <bool BF16, int NG>
 __global__ void __launch_bounds__(256, 2)
 attn_bwd_dq_kernel(const AttnBwdArgs a) {
@@ -181,7 +177,7 @@ attn_bwd_dq_kernel(const AttnBwdArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int g = lane >> 4, c16 = lane & 15;
     int b, h, bx_;
-    block_bhx(a, b, h, bx_);
+    block_bhx(b, h, bx_);
     const int q0 = bx_ * (64 * NG);
     const unsigned lds0 = (unsigned)(size_t)(lds_ptr_t)&smem[0][0][0];
     const KeyList kl = key_list(a, b);
@@ -316,7 +312,7 @@ attn_bwd_dkv_kernel(const AttnBwdArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int g = lane >> 4, c16 = lane & 15;
     int b, h, bx_;
-    block_bhx(a, b, h, bx_);
+    block_bhx(b, h, bx_);
     const int kt0 = bx_ * (64 * NG);
     const KeyList kl = key_list(a, b);
     if (kt0 >= kl.Lk) return;
@@ -534,7 +530,7 @@ attn_bwd_dq_split_kernel(const AttnBwdArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int g = lane >> 4, c16 = lane & 15;
     int b, h, bx_;
-    block_bhx(a, b, h, bx_);
+    block_bhx(b, h, bx_);
     const int q0 = bx_ * (64 * NG);
     const unsigned lds0 = (unsigned)(size_t)(lds_ptr_t)&smem[0][0][0];
     const KeyList kl = key_list(a, b);
@@ -646,7 +642,7 @@ attn_bwd_dkv_split_kernel(const AttnBwdArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int g = lane >> 4, c16 = lane & 15;
     int b, h, bx_;
-    block_bhx(a, b, h, bx_);
+    block_bhx(b, h, bx_);
     const int kt0 = bx_ * (64 * NG);
     const KeyList kl = key_list(a, b);
     if (kt0 >= kl.Lk) return;
@@ -807,7 +803,6 @@ int attention_backward_impl(const void *q, const void *k, const void *v, const v
     VS_CHECK(kv_seg ? max_keys > 0 : Lk > 0, "vs_attention_backward: Lk (or max_keys with kv_seg) must be positive");
     if (nbatch == 0 || Lq == 0) return 0;
     AttnBwdArgs a;
-    { static const int x_ = [] { const char *e = getenv("VS_ATTN_BWD_XCD"); return e ? atoi(e) : 1; }(); a.xcd = x_; }
     a.q = (const unsigned short *)q; a.k = (const unsigned short *)k; a.v = (const unsigned short *)v;
     a.o = (const unsigned short *)o; a.dout = (const unsigned short *)dout; a.lse = lse; a.delta = delta;
     a.dq = (unsigned short *)dq; a.dk = dk; a.dv = dv; a.dk16 = (unsigned short *)dk16; a.dv16 = (unsigned short *)dv16; a.kv_seg = kv_seg; a.q_kvlen = q_kvlen;
@@ -817,26 +812,15 @@ int attention_backward_impl(const void *q, const void *k, const void *v, const v
     const long long rows = (long long)(nbatch - 1) * q_batch_rows + Lq;
     const int keys = kv_seg ? max_keys : Lk;
     dim3 block(256);
-    static const int ng = [] { const char *e = getenv("VS_ATTN_BWD_NG"); return e && atoi(e) == 1 ? 1 : 2; }();   // row groups of 16 per wave
-    const dim3 gq(vs::cdiv(Lq, 64 * ng), H, nbatch), gk(vs::cdiv(keys, 64 * ng), H, nbatch);
+    const dim3 gq(vs::cdiv(Lq, 128), H, nbatch), gk(vs::cdiv(keys, 128), H, nbatch);   // two row groups of 16 per wave
     if (dtype == 2) {
         hipLaunchKernelGGL(attn_delta_kernel<true>, dim3((unsigned)vs::cdiv64(rows * H, 32)), block, 0, stream, a, rows);
-        if (ng == 1) {
-            hipLaunchKernelGGL((attn_bwd_dq_kernel<true, 1>), gq, block, 0, stream, a);
-            hipLaunchKernelGGL((attn_bwd_dkv_kernel<true, 1>), gk, block, 0, stream, a);
-        } else {
-            hipLaunchKernelGGL((attn_bwd_dq_kernel<true, 2>), gq, block, 0, stream, a);
-            hipLaunchKernelGGL((attn_bwd_dkv_kernel<true, 2>), gk, block, 0, stream, a);
-        }
+        hipLaunchKernelGGL((attn_bwd_dq_kernel<true, 2>), gq, block, 0, stream, a);
+        hipLaunchKernelGGL((attn_bwd_dkv_kernel<true, 2>), gk, block, 0, stream, a);
     } else {
         hipLaunchKernelGGL(attn_delta_kernel<false>, dim3((unsigned)vs::cdiv64(rows * H, 32)), block, 0, stream, a, rows);
-        if (ng == 1) {
-            hipLaunchKernelGGL((attn_bwd_dq_kernel<false, 1>), gq, block, 0, stream, a);
-            hipLaunchKernelGGL((attn_bwd_dkv_kernel<false, 1>), gk, block, 0, stream, a);
-        } else {
-            hipLaunchKernelGGL((attn_bwd_dq_kernel<false, 2>), gq, block, 0, stream, a);
-            hipLaunchKernelGGL((attn_bwd_dkv_kernel<false, 2>), gk, block, 0, stream, a);
-        }
+        hipLaunchKernelGGL((attn_bwd_dq_kernel<false, 2>), gq, block, 0, stream, a);
+        hipLaunchKernelGGL((attn_bwd_dkv_kernel<false, 2>), gk, block, 0, stream, a);
     }
     VS_HIP(hipGetLastError());
     return 0;
@@ -883,7 +867,6 @@ extern "C" int vs_attention_backward_split(const void *q_hi, const void *q_lo, c
     VS_CHECK(kv_seg ? max_keys > 0 : Lk > 0, "vs_attention_backward_split: Lk (or max_keys with kv_seg) must be positive");
     if (nbatch == 0 || Lq == 0) return 0;
     AttnBwdArgs a;
-    { static const int x_ = [] { const char *e = getenv("VS_ATTN_BWD_XCD"); return e ? atoi(e) : 1; }(); a.xcd = x_; }
     a.q = (const unsigned short *)q_hi; a.k = (const unsigned short *)k_hi; a.v = (const unsigned short *)v_hi; a.dout = (const unsigned short *)do_hi;
     a.q_lo = (const unsigned short *)q_lo; a.k_lo = (const unsigned short *)k_lo; a.v_lo = (const unsigned short *)v_lo; a.dout_lo = (const unsigned short *)do_lo;
     a.o = nullptr; a.o32 = o; a.dout32 = dout; a.lse = lse; a.delta = delta;
@@ -896,14 +879,10 @@ extern "C" int vs_attention_backward_split(const void *q_hi, const void *q_lo, c
     const int keys = kv_seg ? max_keys : Lk;
     dim3 block(256);
     hipLaunchKernelGGL(attn_delta_f32_kernel, dim3((unsigned)vs::cdiv64(rows * H, 32)), block, 0, stream, a, rows);
-    static const int ngq = [] { const char *e = getenv("VS_ATTN_BWD_NG"); return e && atoi(e) == 1 ? 1 : 2; }();       // row groups of 16 per wave
-    // (dK / dV: two key groups need 64 + 64 + 64 registers for the K | V fragments, the accumulators and the (hi, lo) P | dS fragments alone:
-    // the NG = 2 instantiation spills 102 VGPRs under the 256-register cap -- one group per wave unless VS_ATTN_BWD_NG_KV=2)
-    static const int ngk = [] { const char *e = getenv("VS_ATTN_BWD_NG_KV"); return e && atoi(e) == 2 ? 2 : 1; }();
-    if (ngq == 1) hipLaunchKernelGGL(attn_bwd_dq_split_kernel<1>, dim3(vs::cdiv(Lq, 64), H, nbatch), block, 0, stream, a);
-    else hipLaunchKernelGGL(attn_bwd_dq_split_kernel<2>, dim3(vs::cdiv(Lq, 128), H, nbatch), block, 0, stream, a);
-    if (ngk == 1) hipLaunchKernelGGL(attn_bwd_dkv_split_kernel<1>, dim3(vs::cdiv(keys, 64), H, nbatch), block, 0, stream, a);
-    else hipLaunchKernelGGL(attn_bwd_dkv_split_kernel<2>, dim3(vs::cdiv(keys, 128), H, nbatch), block, 0, stream, a);
+    // dQ: two row groups of 16 per wave.  dK / dV: one -- two key groups need 64 + 64 + 64 registers for the K | V fragments, the accumulators
+    // and the (hi, lo) P | dS fragments alone: the NG = 2 instantiation spilled 102 VGPRs under the 256-register cap
+    hipLaunchKernelGGL(attn_bwd_dq_split_kernel<2>, dim3(vs::cdiv(Lq, 128), H, nbatch), block, 0, stream, a);
+    hipLaunchKernelGGL(attn_bwd_dkv_split_kernel<1>, dim3(vs::cdiv(keys, 64), H, nbatch), block, 0, stream, a);
     VS_HIP(hipGetLastError());
     return 0;
 }

@@ -11,8 +11,6 @@
 // ReLU on the output.
 #include "gemm256.h"
 
-#include <cstdlib>
-
 __device__ __attribute__((aligned(128))) unsigned short vs_zero_page[64] = {0};
 
 namespace {
@@ -36,17 +34,7 @@ struct ConvArgs {
     float acc_scale2;           // split operands, fused head: 2^-e of the packed w2
     int a_packed;               // split operands: `in` is already the packed (hi, lo) image (ops.split_act; any ReLU applied by its producer)
     const float *res2;          // f32 activations: a SECOND residual [N,H,W,Cout] added with `res` (the FeatureFusionBlock's x + rcu(skip), dpt_block.py:196-208)
-    int korder;                 // 256-tile kernels: 0 = K-tiles tap-major (tap, channel block), 1 = channel-block-major (see ConvStager256)
 };
-
-// K-tile order of the 256-tile implicit-GEMM kernels (VS_CONV_KORDER, default 1).  Tap-major, the three kx taps of one image row re-read the
-// same lines kpt K-tiles apart -- x 32 resident workgroups per XCD that is more than the 4 MB L2 holds, and the counters showed the fused
-// Gaussian head fetching 124 GB per step for a 12.9 GB input.  Channel-block-major, the nine taps of one 64-channel block are consecutive
-// K-tiles: the kx re-reads are one K-tile apart.  Only the ORDER of the reduction changes (f32 rounding), not the operands.
-static int conv_korder() {
-    static const int v = [] { const char *e = getenv("VS_CONV_KORDER"); return e ? atoi(e) : 1; }();
-    return v;
-}
 
 // epilogue shared by the conv kernels (accumulators are C^T, see gemm_common.h: a lane holds 4 consecutive output
 // channels of one pixel per fragment): + bias, + residual (8-byte load, added in f32), ReLU, round to 16 bit, one 8-byte
@@ -445,13 +433,13 @@ struct ConvStager256 {
     const unsigned short *pz[2];     // [round] this lane's 16 bytes of the zero page
     unsigned vmask[2][2];            // [A_h][round] bit t: tap t is inside the image (0 for rows past M)
     const unsigned short *pw[2][2];  // [B_h][round]
-    int Cin, Win, kpt, kinv;         // kpt = K-tiles per tap (Cin / 64, any value <= 64: round 5 -- was a power of two), kinv = ceil(2^16 / kpt)
-    int chmajor;                     // K-tile order: 0 (tap, channel block), 1 (channel block, tap) -- late round 5, see conv_korder()
+    int Cin, Win, kpt;               // kpt = K-tiles per tap (Cin / 64, any value <= 64: round 5 -- was a power of two)
+    // K-tile order (channel block, tap): the nine taps of one 64-channel block are consecutive K-tiles, so the kx re-reads of one image row are
+    // one K-tile apart.  Late round 5 -- tap-major, they were kpt K-tiles apart, more than the 4 MB L2 of an XCD holds for its 32 resident
+    // workgroups, and the counters showed the fused Gaussian head fetching 124 GB per step for a 12.9 GB input.
     __device__ __forceinline__ void stage(int u, int kt, unsigned lds) const {
         if (u < 2) {
-            int tap, kc;
-            if (chmajor) { kc = (kt * 7282) >> 16; tap = kt - kc * 9; }     // kt / 9, exact for kt < 576
-            else { tap = (kt * kinv) >> 16; kc = kt - tap * kpt; }          // kt / kpt, exact for kt < 9 * kpt (checked for every kpt <= 64)
+            const int kc = (kt * 7282) >> 16, tap = kt - kc * 9;   // kt / 9, exact for kt < 576
             const int ty = (tap * 11) >> 5;                      // tap / 3 for tap in 0..8
             const int dy = ty - 1, dx = tap - ty * 3 - 1;
             const long long off = (long long)(dy * Win + dx) * Cin + kc * 64;   // wave-uniform
@@ -461,8 +449,7 @@ struct ConvStager256 {
                 glds16(ok ? pa[u][j] + off : pz[j], lds + j * 1024u);
             }
         } else {
-            int wk = kt;
-            if (chmajor) { const int kc = (kt * 7282) >> 16; wk = (kt - kc * 9) * kpt + kc; }     // the weight rows stay [tap][channel]
+            const int kc = (kt * 7282) >> 16, wk = (kt - kc * 9) * kpt + kc;     // the weight rows stay [tap][channel]
             glds16(pw[u - 2][0] + wk * 64, lds);
             glds16(pw[u - 2][1] + wk * 64, lds + 1024u);
         }
@@ -490,7 +477,7 @@ __global__ void __launch_bounds__(512, 1) conv3x3_256_kernel(const ConvArgs g, c
     const int m0 = tm * 256, n0 = tn * 256;
 
     ConvStager256 st;
-    st.Cin = g.Cin; st.Win = g.Win; st.kpt = kpt; st.kinv = (65536 + kpt - 1) / kpt; st.chmajor = g.korder;
+    st.Cin = g.Cin; st.Win = g.Win; st.kpt = kpt;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int q = unit_row256(wid, j, lane);
@@ -530,13 +517,10 @@ struct ConvStager256x128 {
     const unsigned short *pz[2];
     unsigned vmask[2][2];
     const unsigned short *pw[2];     // [round] the B unit: 128 weight rows
-    int Cin, Win, kpt, kinv;         // kpt = K-tiles per tap (Cin / 64, any value <= 64: round 5 -- was a power of two), kinv = ceil(2^16 / kpt)
-    int chmajor;                     // K-tile order: 0 (tap, channel block), 1 (channel block, tap) -- late round 5, see conv_korder()
+    int Cin, Win, kpt;               // K-tile order and kpt as in ConvStager256
     __device__ __forceinline__ void stage(int u, int kt, unsigned lds) const {
         if (u < 2) {
-            int tap, kc;
-            if (chmajor) { kc = (kt * 7282) >> 16; tap = kt - kc * 9; }     // kt / 9, exact for kt < 576
-            else { tap = (kt * kinv) >> 16; kc = kt - tap * kpt; }          // kt / kpt, exact for kt < 9 * kpt (checked for every kpt <= 64)
+            const int kc = (kt * 7282) >> 16, tap = kt - kc * 9;   // kt / 9, exact for kt < 576
             const int ty = (tap * 11) >> 5;
             const int dy = ty - 1, dx = tap - ty * 3 - 1;
             const long long off = (long long)(dy * Win + dx) * Cin + kc * 64;
@@ -546,8 +530,7 @@ struct ConvStager256x128 {
                 glds16(ok ? pa[u][j] + off : pz[j], lds + j * 1024u);
             }
         } else {
-            int wk = kt;
-            if (chmajor) { const int kc = (kt * 7282) >> 16; wk = (kt - kc * 9) * kpt + kc; }
+            const int kc = (kt * 7282) >> 16, wk = (kt - kc * 9) * kpt + kc;
             glds16(pw[0] + wk * 64, lds);
             glds16(pw[1] + wk * 64, lds + 1024u);
         }
@@ -576,7 +559,7 @@ __global__ void __launch_bounds__(512, 1) conv3x3_256x128_split_kernel(const Con
     const int tm = bid / tiles_n, tn = bid % tiles_n;
     const int m0 = tm * 256, n0 = tn * 128;
     ConvStager256x128 st;
-    st.Cin = g.Cin; st.Win = g.Win; st.kpt = kpt; st.kinv = (65536 + kpt - 1) / kpt; st.chmajor = g.korder;
+    st.Cin = g.Cin; st.Win = g.Win; st.kpt = kpt;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int q = unit_row256(wid, j, lane);                 // unit row 0..127 this lane stages
@@ -1078,10 +1061,8 @@ static int conv3x3_entry(const void *in, const void *w, const float *bias, const
     VS_CHECK(!in_packed || (dtype == 4 && relu_in == 0), "vs_conv3x3_split_nhwc: a packed input is a split-class operand that carries its ReLU already");
     ConvArgs g{(const unsigned short *)in, (const unsigned short *)w, bias, (const unsigned short *)residual, (unsigned short *)out,
                Nimg, H, W, Cin, Cout, relu_in, relu_out, Hin, Win, stride, nullptr, nullptr, nullptr, 0, 0, 0, acc_scale, 1.f, in_packed, residual2};
-    g.korder = conv_korder();
     VS_CHECK(!residual2 || ((dtype == 3 || dtype == 4) && relu_out != 2), "vs_conv3x3_nhwc: a second residual needs f32 activations (dtype 3 / 4) and no mask epilogue");
     const long long M = (long long)Nimg * H * W;
-    static const int force = [] { const char *e = getenv("VS_CONV_MI"); return e ? atoi(e) : 0; }();
     int cshift = -1;
     for (int sft = 0; sft < 4; ++sft)
         if (Cin == (64 << sft)) cshift = sft;
@@ -1089,18 +1070,17 @@ static int conv3x3_entry(const void *in, const void *w, const float *bias, const
     // the DPT reassemble / layer_rn convolutions and the stride-2 768 -> 768 convolution used to run on the 4-wave kernels at 170-270 TF/s)
     const int kpt_any = (Cin % 64 == 0 && Cin / 64 <= 64) ? Cin / 64 : -1;
     const long long t256 = vs::cdiv64(M, 256) * vs::cdiv(Cout, 256);
-    static const int t256_min_env = [] { const char *e = getenv("VS_CONV_T256_MIN"); return e ? atoi(e) : 0; }();
     // >= 150 tiles (round 5; was 224): a 59 %-full round of 256 x 256 tiles beats the 4-wave kernel's one and a half rounds at two workgroups
     // per CU in the split class (16 x 16 maps of the bench step: 0.21 -> 0.17 ms per convolution); 8 x 8 maps (48 tiles) stay where they were
-    const long long t256_min = t256_min_env > 0 ? t256_min_env : (dtype == 4 ? 150 : 224);
-    if (force != 8 && force != 4 && dtype == 4 && cshift < 0 && kpt_any > 0 && Cout % 256 == 0 && (9 * kpt_any) % 2 == 0 && t256 >= t256_min && !g.a_packed) {
+    const long long t256_min = dtype == 4 ? 150 : 224;
+    if (dtype == 4 && cshift < 0 && kpt_any > 0 && Cout % 256 == 0 && (9 * kpt_any) % 2 == 0 && t256 >= t256_min && !g.a_packed) {
         dim3 grid((unsigned)t256), block(512);
         if (relu_in) hipLaunchKernelGGL((conv3x3_256_kernel<kDtSplit, true>), grid, block, 0, stream, g, kpt_any);
         else hipLaunchKernelGGL((conv3x3_256_kernel<kDtSplit, false>), grid, block, 0, stream, g, kpt_any);
         VS_HIP(hipGetLastError());
         return 0;
     }
-    if (force != 8 && force != 4 && cshift >= 0 && Cout % 256 == 0 && (9 * Cin / 64) % 2 == 0 && t256 >= t256_min) {
+    if (cshift >= 0 && Cout % 256 == 0 && (9 * Cin / 64) % 2 == 0 && t256 >= t256_min) {
         dim3 grid((unsigned)t256), block(512);
         if (dtype == 4) {
             if (g.a_packed) hipLaunchKernelGGL((conv3x3_256_kernel<kDtSplit, false, 0, true>), grid, block, 0, stream, g, 1 << cshift);
@@ -1122,8 +1102,7 @@ static int conv3x3_entry(const void *in, const void *w, const float *bias, const
     const long long big = vs::cdiv64(M, 256) * vs::cdiv(Cout, BN);
     if (dtype == 4) {
         VS_CHECK(Cin % 64 == 0, "vs_conv3x3_split_nhwc: Cin must be a multiple of 32");
-        static const int no128 = [] { const char *e = getenv("VS_CONV_SPLIT_NO256X128"); return e ? atoi(e) : 0; }();
-        if (!no128 && cshift >= 0 && Cout % 128 == 0 && Cout % 256 != 0 && (9 * Cin / 64) % 2 == 0 && big >= 224) {   // (Cout = 256 maps too small for the 256 x 256 kernel: the 4-wave kernel is 8 % faster there, measured)
+        if (cshift >= 0 && Cout % 128 == 0 && Cout % 256 != 0 && (9 * Cin / 64) % 2 == 0 && big >= 224) {   // (Cout = 256 maps too small for the 256 x 256 kernel: the 4-wave kernel is 8 % faster there, measured)
             dim3 grid((unsigned)(vs::cdiv64(M, 256) * (Cout / 128))), block(512);
             if (g.a_packed) hipLaunchKernelGGL((conv3x3_256x128_split_kernel<false, false, true>), grid, block, 0, stream, g, 1 << cshift);
             else if (relu_in) hipLaunchKernelGGL((conv3x3_256x128_split_kernel<true, false>), grid, block, 0, stream, g, 1 << cshift);
@@ -1132,17 +1111,15 @@ static int conv3x3_entry(const void *in, const void *w, const float *bias, const
             return 0;
         }
         VS_CHECK(!g.a_packed, "vs_conv3x3_split_nhwc: a packed input is taken by the 256 x 256 and 256 x 128 tile kernels only (this shape runs on the 4-wave kernel)");
-        static const int smi = [] { const char *e = getenv("VS_CONV_SPLIT_MI"); return e ? atoi(e) : 0; }();
         // round 6, small batches (one 8-view scene: 16 x 16 / 32 x 32 maps = 2 048 / 8 192 pixels x 256 channels = 32 / 128 tiles of 128 x 128 for
-        // 256 CUs): 64-row tiles (MI = 2, the same kernel) double the workgroups.  VS_CONV_MI2=0 for the A/B.
-        static const int mi2 = [] { const char *e = getenv("VS_CONV_MI2"); return e ? atoi(e) : 1; }();
+        // 256 CUs): 64-row tiles (MI = 2, the same kernel) double the workgroups.
         const long long t4 = vs::cdiv64(M, 128) * vs::cdiv(Cout, BN);
-        if ((big >= 512 && smi != 4) || smi == 8) hipLaunchKernelGGL((conv3x3_kernel<kDtSplit, 8>), dim3((unsigned)big), dim3(256), 0, stream, g);
-        else if (mi2 && smi == 0 && t4 <= 192 && M > 64) hipLaunchKernelGGL((conv3x3_kernel<kDtSplit, 2>), dim3((unsigned)(vs::cdiv64(M, 64) * vs::cdiv(Cout, BN))), dim3(256), 0, stream, g);
+        if (big >= 512) hipLaunchKernelGGL((conv3x3_kernel<kDtSplit, 8>), dim3((unsigned)big), dim3(256), 0, stream, g);
+        else if (t4 <= 192 && M > 64) hipLaunchKernelGGL((conv3x3_kernel<kDtSplit, 2>), dim3((unsigned)(vs::cdiv64(M, 64) * vs::cdiv(Cout, BN))), dim3(256), 0, stream, g);
         else hipLaunchKernelGGL((conv3x3_kernel<kDtSplit, 4>), dim3((unsigned)t4), dim3(256), 0, stream, g);
     } else if (dtype == 3) {
         hipLaunchKernelGGL((conv3x3_kernel<kDtF32, 4>), dim3((unsigned)(vs::cdiv64(M, 128) * vs::cdiv(Cout, BN))), dim3(256), 0, stream, g);
-    } else if ((big >= 256 || force == 8) && force != 4) {
+    } else if (big >= 256) {
         dim3 grid((unsigned)big);
         if (dtype == 2) hipLaunchKernelGGL((conv3x3_kernel<true, 8>), grid, dim3(256), 0, stream, g);
         else hipLaunchKernelGGL((conv3x3_kernel<false, 8>), grid, dim3(256), 0, stream, g);
@@ -1198,7 +1175,6 @@ extern "C" int vs_conv3x3_head1x1_nhwc(const void *in, const void *w, const floa
     VS_CHECK(relu_out == 0 || relu_out == 1, "vs_conv3x3_head1x1_nhwc: relu_out must be 0 or 1");
     ConvArgs g{(const unsigned short *)in, (const unsigned short *)w, bias, nullptr, nullptr, Nimg, H, W, Cin, Cout, relu_in, relu_out, H, W, 1,
                (const unsigned short *)w2, bias2, (unsigned short *)out2, C2, C2pad, ld2, 1.f, 1.f};
-    g.korder = conv_korder();
     if (Cout == 256) {
         int cshift = -1;
         for (int sft = 0; sft < 4; ++sft)
@@ -1246,12 +1222,10 @@ extern "C" int vs_conv3x3_head_dot_split_nhwc(const float *in, const void *wp, f
     VS_CHECK((((uintptr_t)in | (uintptr_t)wp | (uintptr_t)out2 | (uintptr_t)bias2) & 15) == 0, "vs_conv3x3_head_dot_split_nhwc: 16-byte alignment required");
     ConvArgs g{(const unsigned short *)in, (const unsigned short *)wp, bias, nullptr, nullptr, Nimg, H, W, 2 * Cin, 128, relu_in, relu_out, H, W, 1,
                (const unsigned short *)w2, bias2, (unsigned short *)out2, C2, C2, ld2, acc_scale, 1.f};
-    g.korder = conv_korder();
     int cshift = -1;
     for (int sft = 0; sft < 4; ++sft)
         if (2 * Cin == (64 << sft)) cshift = sft;
-    static const int no128 = [] { const char *e = getenv("VS_CONV_SPLIT_NO256X128"); return e ? atoi(e) : 0; }();
-    const bool tile128 = !no128 && cshift >= 0 && (9 * 2 * Cin / 64) % 2 == 0 && !relu_in;
+    const bool tile128 = cshift >= 0 && (9 * 2 * Cin / 64) % 2 == 0 && !relu_in;
     VS_CHECK(!in_packed || tile128, "vs_conv3x3_head_dot_split_nhwc: a packed input needs the 256 x 128 tile kernel (Cin in {32, 64, 128, 256}, no relu_in)");
     if (tile128 && in_packed)
         hipLaunchKernelGGL((conv3x3_256x128_split_kernel<false, true, true>), dim3((unsigned)(M / 256)), dim3(512), 0, stream, g, 1 << cshift);
@@ -1285,7 +1259,6 @@ extern "C" int vs_conv3x3_head1x1_split_nhwc(const float *in, const void *wp, fl
              "vs_conv3x3_head1x1_split_nhwc: 16-byte alignment required");
     ConvArgs g{(const unsigned short *)in, (const unsigned short *)wp, bias, nullptr, nullptr, Nimg, H, W, 2 * Cin, 256, 0, relu_out, H, W, 1,
                (const unsigned short *)w2p, bias2, (unsigned short *)out2, C2, C2pad, ld2, acc_scale, acc_scale2};
-    g.korder = conv_korder();
     dim3 grid((unsigned)(M / 256)), block(512);
     g.a_packed = in_packed;
 #define VS_HEAD(NF_) { if (in_packed) hipLaunchKernelGGL((conv3x3_256_kernel<kDtSplit, false, NF_, true>), grid, block, 0, stream, g, 1 << cshift); \
@@ -1314,8 +1287,7 @@ extern "C" int vs_upsample2x_nhwc(const void *in, const void *add, void *out, in
     if (dtype == 3) {
         VS_CHECK(C % 4 == 0, "vs_upsample2x_nhwc: C=%d must be a multiple of 4", C);
         if ((long long)Nimg * H * W * C <= 0) return 0;
-        static const int oldk = [] { const char *e = getenv("VS_UPSAMPLE_F32_OLD"); return e ? atoi(e) : 0; }();
-        if (H >= 2 && W >= 2 && !oldk) {
+        if (H >= 2 && W >= 2) {
             const int rows = Nimg * H, gy = rows < 32768 ? rows : 32768;
             hipLaunchKernelGGL(upsample2x_f32_block_kernel, dim3((unsigned)vs::cdiv(W * (C / 4), 256), gy, vs::cdiv(rows, gy)), dim3(256), 0, stream,
                                (const float *)in, (const float *)add, (float *)out, Nimg, H, W, C, relu_add, pack_out);

@@ -22,8 +22,6 @@
 // (e.g. the 257 image tokens of a frame behind the frame's camera token).
 #include "gemm256.h"
 
-#include <cstdlib>
-
 namespace {
 
 template <int BF16, int EPI, int MI>
@@ -667,28 +665,25 @@ int launch_tail(const GemmArgs &g, int rem, int epi, hipStream_t stream) {
     t.m_lo = g.M - rem;
     // a tail is a handful of tiles walking all of K serially: for the f32 residual epilogue split K over up to 8 workgroups
     // per tile (>= 8 k-steps each) and let the partial sums meet through f32 atomics
-    static const int no_ksplit = [] { const char *e = getenv("VS_GEMM_NO_KSPLIT"); return e ? atoi(e) : 0; }();
-    if (epi == 2 && rem > 64 && !no_ksplit && !g.resid && !vs::deterministic()) {   // (split-K partial sums meet in out: it must already hold the residual)
+    if (epi == 2 && rem > 64 && !g.resid && !vs::deterministic()) {   // (split-K partial sums meet in out: it must already hold the residual)
         const int tiles = vs::cdiv(rem, 128) * vs::cdiv(g.N, BN);
         int ks = 1;
         while (ks < 8 && (g.K / 32) % (ks * 2) == 0 && g.K / 32 / (ks * 2) >= 8 && tiles * ks * 2 <= 512) ks *= 2;
         t.ksplit = ks;
     }
     // (the RoPE epilogue pairs columns 16 apart and a packed output is written in 32-column blocks: only the tile kernels hold those in one
-    // workgroup).  Round 4: the weight-streaming kernel takes row groups of 64 (blockIdx.y) and packed A rows, so VS_GEMM_TAIL_SMALLM=256 sends
-    // the 192-row tails of the bench step to it (plain stores of whole-K sums instead of the K-split tiles' f32 atomics).  Measured same-box:
-    // 246.6 / 248.3 vs 247.6 / 247.7 ms per step -- no gain (A is re-read by each of the N / 16 column workgroups); the default stays 64.
-    static const int tail_rows = [] { const char *e = getenv("VS_GEMM_TAIL_SMALLM"); return e ? atoi(e) : 64; }();
-    // round 5: tails of 65 .. 256 rows of the split class run on the skinny kernel (every epilogue, packed A / packed output included)
-    static const int skinny = [] { const char *e = getenv("VS_GEMM_SKINNY"); return e ? atoi(e) : 1; }();
+    // workgroup).  Round 4: the weight-streaming kernel takes row groups of 64 (blockIdx.y) and packed A rows, so sending the 192-row tails
+    // of the bench step to it (plain stores of whole-K sums instead of the K-split tiles' f32 atomics) was measured same-box:
+    // 246.6 / 248.3 vs 247.6 / 247.7 ms per step -- no gain (A is re-read by each of the N / 16 column workgroups); tails of <= 64 rows stay.
+    // Round 5: tails of 65 .. 256 rows of the split class run on the skinny kernel (every epilogue, packed A / packed output included)
     if constexpr (BF16 == kDtSplit || BF16 == 0 || BF16 == 1) {   // (split class and, since late round 5, the 16-bit classes)
         // (<= 64 rows stay on the weight-streaming kernel where it applies; the RoPE epilogue and packed outputs, which it does not have, come here)
-        if (skinny && rem <= 256 && g.K % 64 == 0 && (rem > 64 || skinny == 2 || epi == 4 || epi == 5 || g.out_packed) && (BF16 == kDtSplit || (!g.a_packed && !g.out_packed))) {
+        if (rem <= 256 && g.K % 64 == 0 && (rem > 64 || epi == 4 || epi == 5 || g.out_packed) && (BF16 == kDtSplit || (!g.a_packed && !g.out_packed))) {
             t.ksplit = 1;
             return launch_skinny<BF16>(t, epi, stream);
         }
     }
-    if (rem <= (BF16 == kDtSplit ? tail_rows : 64) && epi != 4 && epi != 5 && !g.out_packed && (BF16 == kDtSplit || !g.a_packed)) {
+    if (rem <= 64 && epi != 4 && epi != 5 && !g.out_packed && (BF16 == kDtSplit || !g.a_packed)) {
         t.ksplit = 1;
         return launch_smallm<BF16>(t, epi, stream);
     }
@@ -706,17 +701,12 @@ int launch_f32(const GemmArgs &g, int epi, hipStream_t stream) {
 
 template <int BF16>
 int launch(const GemmArgs &g, int epi, hipStream_t stream) {
-    // VS_GEMM_MI = 4 | 8 | 16 forces the 128x128 | 256x128 | 256x256 kernel (benchmarks, tests).
-    static const int force = [] { const char *e = getenv("VS_GEMM_MI"); return e ? atoi(e) : 0; }();
-    if (g.M <= 64 && force == 0 && epi != 4 && epi != 5 && !g.out_packed && (BF16 == kDtSplit || !g.a_packed)) return launch_smallm<BF16>(g, epi, stream);
+    if (g.M <= 64 && epi != 4 && epi != 5 && !g.out_packed && (BF16 == kDtSplit || !g.a_packed)) return launch_smallm<BF16>(g, epi, stream);
     if constexpr (BF16 == kDtSplit || BF16 == 0 || BF16 == 1) {   // camera-token GEMMs and other launches of <= 256 rows: the skinny kernel (round 5)
-        static const int skinny = [] { const char *e = getenv("VS_GEMM_SKINNY"); return e ? atoi(e) : 1; }();
-        if (skinny && force == 0 && g.M - g.m_lo <= 256 && g.K % 64 == 0 && g.ntaps == 0 && !g.partials && g.ksplit <= 1 && g.a_sup_extra == 0 && g.a_kstride == 32 &&
+        if (g.M - g.m_lo <= 256 && g.K % 64 == 0 && g.ntaps == 0 && !g.partials && g.ksplit <= 1 && g.a_sup_extra == 0 && g.a_kstride == 32 &&
             (BF16 == kDtSplit || (!g.a_packed && !g.out_packed)))
             return launch_skinny<BF16>(g, epi, stream);
     }
-    if (force == 8) return launch_mi<BF16, 8>(g, epi, stream);
-    if (force == 4) return launch_mi<BF16, 4>(g, epi, stream);
     // 256x256 tiles run one 8-wave workgroup per CU, i.e. in rounds of 256 tiles, and a partly filled round costs as much
     // as a full one (M = frames * 257 tokens never divides).  So the big tiles only get as many rows as fill whole rounds;
     // the remaining rows are finished by a launch of small tiles (128x128, 3 workgroups per CU) or, for <= 64 rows, the
@@ -737,7 +727,7 @@ int launch(const GemmArgs &g, int epi, hipStream_t stream) {
         const bool split = !nearly_full && rem > 0 && mt_main > 0 && cost_split < (double)rounds_all - 0.05;
         // (a round that is >= 70 % full still beats the 256x128 tiles: 8 scenes x 257 tokens x 768 columns = 195 tiles, 385 vs 391 ms per
         // split-class training step)
-        if (force == 16 || split || tiles_one * 100 >= rounds_all * 256 * 70) {
+        if (split || tiles_one * 100 >= rounds_all * 256 * 70) {
             GemmArgs main_g = g;
             if (split) main_g.M = rows_main;
             int rc = launch_256<BF16>(main_g, epi, stream);
@@ -761,11 +751,10 @@ int launch(const GemmArgs &g, int epi, hipStream_t stream) {
     if (split) main_g.M = g.M - rem;
     // Round 6, small batches (one 8-view scene = 2 056 rows): the residual epilogue's GEMMs (attention projection, fc2: N = 1024 / 768) are
     // 136 / 102 tiles of 128 x 128 -- half the chip for one pass over K.  64-row tiles (MI = 2: the same kernel, each wave a 32 x 64 slab)
-    // double the workgroups: VS_GEMM_MI2=0 for the A/B.
+    // double the workgroups.
     if constexpr (BF16 == kDtSplit) {
-        static const int mi2 = [] { const char *e = getenv("VS_GEMM_MI2"); return e ? atoi(e) : 1; }();
         const long long tiles4 = (long long)vs::cdiv(main_g.M - main_g.m_lo, 128) * tiles_n;
-        if (mi2 && mi == 4 && epi == 2 && g.ntaps == 0 && g.ksplit <= 1 && !g.partials && tiles4 <= 192 && main_g.M - main_g.m_lo > 64) {
+        if (mi == 4 && epi == 2 && g.ntaps == 0 && g.ksplit <= 1 && !g.partials && tiles4 <= 192 && main_g.M - main_g.m_lo > 64) {
             const long long nwg = (long long)vs::cdiv(main_g.M - main_g.m_lo, 64) * tiles_n;
             hipLaunchKernelGGL((gemm_kernel<kDtSplit, 2, 2>), dim3((unsigned)nwg, 1), dim3(256), 0, stream, main_g);
             if (!split) return 0;
@@ -778,13 +767,6 @@ int launch(const GemmArgs &g, int epi, hipStream_t stream) {
     int rc = mi == 8 ? launch_mi<BF16, 8>(main_g, epi, stream) : launch_mi<BF16, 4>(main_g, epi, stream);
     if (rc || !split) return rc;
     return launch_tail<BF16>(g, rem, epi, stream);
-}
-
-// XCD-aware logical block ids in the split-K / tap-fused weight-gradient kernels (gemm256.h splitk_logical_block): VS_WGRAD_XCD=0 restores the
-// plain blockIdx order for an A/B.
-static int wgrad_xcd() {
-    static const int v = [] { const char *e = getenv("VS_WGRAD_XCD"); return e ? atoi(e) : 1; }();
-    return v;
 }
 
 // out[t][m, n] += sum_s partials[((s * ntaps + t) * M + m) * N + n]: second stage of a weight-gradient GEMM with a workspace.
@@ -851,9 +833,8 @@ __global__ void __launch_bounds__(256) splitk_reduce_t_kernel(const float *__res
 // one they meet through f32 atomics.
 template <int BF16>
 int launch_wgrad(GemmArgs &g, int ksplit, float *ws, long long ws_bytes, int accumulate, hipStream_t stream) {
-    static const int no256 = [] { const char *e = getenv("VS_WGRAD_NO256"); return e ? atoi(e) : 0; }();
     const int ntaps = g.ntaps > 0 ? g.ntaps : 1;
-    const bool big = !no256 && g.M % 256 == 0 && g.N % 256 == 0 && g.K % (128 * ksplit) == 0;
+    const bool big = g.M % 256 == 0 && g.N % 256 == 0 && g.K % (128 * ksplit) == 0;
     const int slices = big ? ksplit : (ksplit > 1 ? ksplit : 2);  // gemm_kernel always runs >= 2 slices in this mode
     const long long need = (long long)slices * ntaps * g.M * g.N * (long long)sizeof(float);
     g.partials = nullptr;
@@ -916,17 +897,12 @@ int gemm_entry(const char *fn, const void *A, const void *W, const float *bias, 
     g.a_grp_in = a_grp_in > 0 ? a_grp_in : (M > 0 ? M : 1);
     g.a_grp_out = a_grp_out > 0 ? a_grp_out : g.a_grp_in;
     g.a_grp_off = a_grp_off;
-    g.m_lo = 0;
-    g.a_sup_in = 0x7fffffff; g.a_sup_extra = 0; g.a_kstride = 32; g.ksplit = 1; g.ntaps = 0; g.tap_out_stride = 0; g.partials = nullptr; g.a_slice_stride = 0; g.w_slice_stride = 0; g.k_valid = 0; g.conv_H = 0; g.conv_W = 0;
     g.rope_pos = rope_pos; g.rope_kind = rope_kind; g.rope_C = rope_C;
-    { static const int stg = [] { const char *e = getenv("VS_GEMM_STAGGER"); return e ? atoi(e) : 0; }(); g.stagger = stg; }
-    { static const int rb = [] { const char *e = getenv("VS_GEMM_ROW_BAND"); return e ? atoi(e) : 0; }(); g.row_band = rb; }
     g.rope_l2base = base2d > 0.f ? log2f(base2d) : 0.f;
     g.rope_l2theta = theta1d > 0.f ? log2f(theta1d) : 0.f;
     g.acc_scale = acc_scale;
     g.a_packed = a_packed;
     g.out_packed = out_packed;
-    g.tap_on_a = 0;
     // split operands (kDtSplit) take the 16-bit classes' routing: whole rounds of 256 x 256 tiles + a tail launch (K counts 2-byte units
     // of the f32 rows; every stage pair / K-tile of the kernels is one 128-byte block of 32 k)
     const int rc = dtype == 4 ? launch<kDtSplit>(g, epilogue, stream)
@@ -1078,14 +1054,11 @@ extern "C" int vs_gemm_wgrad(const void *A, const void *W, float *out, int32_t M
         K *= 2; lda *= 2; ldw *= 2; a_slice_stride *= 2; w_slice_stride *= 2;
     }
     GemmArgs g;
-    g.A = A; g.W = W; g.bias = nullptr; g.out = out; g.gate = nullptr; g.resid = nullptr;
+    g.A = A; g.W = W; g.out = out;
     g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = ldw; g.ldo = ldo;
-    g.grp_in = M; g.grp_out = M; g.grp_off = 0; g.gate_rows = M; g.gate_ld = N;
-    g.a_grp_in = M; g.a_grp_out = M; g.a_grp_off = 0; g.m_lo = 0;
-    g.a_sup_in = 0x7fffffff; g.a_sup_extra = 0; g.a_kstride = 32;
-    g.rope_pos = nullptr; g.rope_kind = nullptr; g.rope_C = 0; g.rope_l2base = 0.f; g.rope_l2theta = 0.f; g.stagger = 0; g.row_band = wgrad_xcd(); g.acc_scale = 1.f; g.a_packed = 0; g.out_packed = 0; g.tap_on_a = 0;
+    g.grp_in = M; g.grp_out = M; g.gate_rows = M; g.gate_ld = N; g.a_grp_in = M; g.a_grp_out = M;
     g.ntaps = ntaps; g.tap_out_stride = ntaps > 0 ? tap_out_stride : 0;
-    g.a_slice_stride = a_slice_stride; g.w_slice_stride = w_slice_stride; g.k_valid = 0; g.conv_H = 0; g.conv_W = 0;
+    g.a_slice_stride = a_slice_stride; g.w_slice_stride = w_slice_stride;
     VS_CHECK(a_slice_stride >= 0 && w_slice_stride >= 0, "vs_gemm_wgrad: negative slice stride");
     for (int t = 0; t < 9; ++t) g.tap_shift[t] = t < ntaps ? shifts[t] * (dtype == 4 ? 2 : 1) : 0;
     g.tap_on_a = dtype == 4 ? 1 : 0;
@@ -1117,14 +1090,10 @@ extern "C" int vs_gemm_wgrad_tn(const void *A, const void *W, float *out, int32_
     const long long Kpad = ((long long)Kred + unit - 1) / unit * unit;
     VS_CHECK(Kpad < 2147483647LL, "vs_gemm_wgrad_tn: reduction too long");
     GemmArgs g;
-    g.A = A; g.W = W; g.bias = nullptr; g.out = out; g.gate = nullptr; g.resid = nullptr;
+    g.A = A; g.W = W; g.out = out;
     g.M = M; g.N = N; g.K = (int)Kpad; g.lda = lda; g.ldw = ldw; g.ldo = ldo;
-    g.grp_in = M; g.grp_out = M; g.grp_off = 0; g.gate_rows = M; g.gate_ld = N;
-    g.a_grp_in = M; g.a_grp_out = M; g.a_grp_off = 0; g.m_lo = 0;
-    g.a_sup_in = 0x7fffffff; g.a_sup_extra = 0; g.a_kstride = 32;
-    g.rope_pos = nullptr; g.rope_kind = nullptr; g.rope_C = 0; g.rope_l2base = 0.f; g.rope_l2theta = 0.f; g.stagger = 0; g.row_band = wgrad_xcd(); g.acc_scale = 1.f; g.a_packed = 0; g.out_packed = 0; g.tap_on_a = 0;
-    g.ntaps = 0; g.tap_out_stride = 0; g.a_slice_stride = 0; g.w_slice_stride = 0;
-    g.ksplit = ksplit; g.k_valid = Kred; g.partials = nullptr; g.conv_H = 0; g.conv_W = 0;
+    g.grp_in = M; g.grp_out = M; g.gate_rows = M; g.gate_ld = N; g.a_grp_in = M; g.a_grp_out = M;
+    g.ksplit = ksplit; g.k_valid = Kred;
     const long long need = (long long)ksplit * M * N * (long long)sizeof(float);
     if (workspace) {
         VS_CHECK(workspace_bytes >= need, "vs_gemm_wgrad_tn: workspace of %lld bytes given, %lld needed", (long long)workspace_bytes, need);
@@ -1163,14 +1132,10 @@ extern "C" int vs_gemm_wgrad_split_atn(const float *A, const void *Wp, float *ou
     VS_CHECK((((uintptr_t)A | (uintptr_t)Wp) & 15) == 0, "vs_gemm_wgrad_split_atn: A and Wp must be 16-byte aligned");
     VS_CHECK(accumulate || workspace, "vs_gemm_wgrad_split_atn: accumulate = 0 (overwrite out) needs a workspace");
     GemmArgs g;
-    g.A = A; g.W = Wp; g.bias = nullptr; g.out = out; g.gate = nullptr; g.resid = nullptr;
+    g.A = A; g.W = Wp; g.out = out;
     g.M = M; g.N = N; g.K = Kpad; g.lda = lda; g.ldw = 2 * ldw; g.ldo = ldo;
-    g.grp_in = M; g.grp_out = M; g.grp_off = 0; g.gate_rows = M; g.gate_ld = N;
-    g.a_grp_in = M; g.a_grp_out = M; g.a_grp_off = 0; g.m_lo = 0;
-    g.a_sup_in = 0x7fffffff; g.a_sup_extra = 0; g.a_kstride = 32;
-    g.rope_pos = nullptr; g.rope_kind = nullptr; g.rope_C = 0; g.rope_l2base = 0.f; g.rope_l2theta = 0.f; g.stagger = 0; g.row_band = wgrad_xcd(); g.acc_scale = 1.f; g.a_packed = 0; g.out_packed = 0; g.tap_on_a = 0;
-    g.ntaps = 0; g.tap_out_stride = 0; g.a_slice_stride = 0; g.w_slice_stride = 0;
-    g.ksplit = ksplit; g.k_valid = Kred; g.partials = nullptr; g.conv_H = 0; g.conv_W = 0;
+    g.grp_in = M; g.grp_out = M; g.gate_rows = M; g.gate_ld = N; g.a_grp_in = M; g.a_grp_out = M;
+    g.ksplit = ksplit; g.k_valid = Kred;
     const long long need = (long long)ksplit * M * N * (long long)sizeof(float);
     if (workspace) {
         VS_CHECK(workspace_bytes >= need, "vs_gemm_wgrad_split_atn: workspace of %lld bytes given, %lld needed", (long long)workspace_bytes, need);
@@ -1209,14 +1174,11 @@ extern "C" int vs_conv3x3_wgrad_split_atn(const float *x, const void *dyTp, floa
     VS_CHECK((((uintptr_t)x | (uintptr_t)dyTp) & 15) == 0, "vs_conv3x3_wgrad_split_atn: x and dyTp must be 16-byte aligned");
     VS_CHECK(accumulate || workspace, "vs_conv3x3_wgrad_split_atn: accumulate = 0 (overwrite out) needs a workspace");
     GemmArgs g;
-    g.A = x; g.W = dyTp; g.bias = nullptr; g.out = out; g.gate = nullptr; g.resid = nullptr;
+    g.A = x; g.W = dyTp; g.out = out;
     g.M = Cin; g.N = Cout; g.K = Ppad; g.lda = Cin; g.ldw = 2 * ldw; g.ldo = Cout;
-    g.grp_in = Cin; g.grp_out = Cin; g.grp_off = 0; g.gate_rows = Cin; g.gate_ld = Cout;
-    g.a_grp_in = Cin; g.a_grp_out = Cin; g.a_grp_off = 0; g.m_lo = 0;
-    g.a_sup_in = 0x7fffffff; g.a_sup_extra = 0; g.a_kstride = 32;
-    g.rope_pos = nullptr; g.rope_kind = nullptr; g.rope_C = 0; g.rope_l2base = 0.f; g.rope_l2theta = 0.f; g.stagger = 0; g.row_band = wgrad_xcd(); g.acc_scale = 1.f; g.a_packed = 0; g.out_packed = 0; g.tap_on_a = 1;
-    g.ntaps = 9; g.tap_out_stride = (long long)Cin * Cout; g.a_slice_stride = 0; g.w_slice_stride = 0;
-    g.ksplit = ksplit; g.k_valid = (int)P; g.partials = nullptr; g.conv_H = H; g.conv_W = W;
+    g.grp_in = Cin; g.grp_out = Cin; g.gate_rows = Cin; g.gate_ld = Cout; g.a_grp_in = Cin; g.a_grp_out = Cin;
+    g.tap_on_a = 1; g.ntaps = 9; g.tap_out_stride = (long long)Cin * Cout;
+    g.ksplit = ksplit; g.k_valid = (int)P; g.conv_H = H; g.conv_W = W;
     const long long need = (long long)ksplit * 9 * Cin * Cout * (long long)sizeof(float);
     if (workspace) {
         VS_CHECK(workspace_bytes >= need, "vs_conv3x3_wgrad_split_atn: workspace of %lld bytes given, %lld needed", (long long)workspace_bytes, need);
@@ -1259,14 +1221,11 @@ extern "C" int vs_conv3x3_wgrad_tn(const void *x, const void *dy, float *out, in
     const long long Kpad = (P + unit - 1) / unit * unit;
     VS_CHECK(Kpad < 2147483647LL, "vs_conv3x3_wgrad_tn: too many pixels");
     GemmArgs g;
-    g.A = x; g.W = dy; g.bias = nullptr; g.out = out; g.gate = nullptr; g.resid = nullptr;
+    g.A = x; g.W = dy; g.out = out;
     g.M = Cin; g.N = Cout; g.K = (int)Kpad; g.lda = Cin; g.ldw = Cout; g.ldo = Cout;
-    g.grp_in = Cin; g.grp_out = Cin; g.grp_off = 0; g.gate_rows = Cin; g.gate_ld = Cout;
-    g.a_grp_in = Cin; g.a_grp_out = Cin; g.a_grp_off = 0; g.m_lo = 0;
-    g.a_sup_in = 0x7fffffff; g.a_sup_extra = 0; g.a_kstride = 32;
-    g.rope_pos = nullptr; g.rope_kind = nullptr; g.rope_C = 0; g.rope_l2base = 0.f; g.rope_l2theta = 0.f; g.stagger = 0; g.row_band = wgrad_xcd(); g.acc_scale = 1.f; g.a_packed = 0; g.out_packed = 0; g.tap_on_a = 0;
-    g.ntaps = 9; g.tap_out_stride = (long long)Cin * Cout; g.a_slice_stride = 0; g.w_slice_stride = 0;
-    g.ksplit = ksplit; g.k_valid = (int)P; g.partials = nullptr; g.conv_H = H; g.conv_W = W;
+    g.grp_in = Cin; g.grp_out = Cin; g.gate_rows = Cin; g.gate_ld = Cout; g.a_grp_in = Cin; g.a_grp_out = Cin;
+    g.ntaps = 9; g.tap_out_stride = (long long)Cin * Cout;
+    g.ksplit = ksplit; g.k_valid = (int)P; g.conv_H = H; g.conv_W = W;
     const long long need = (long long)ksplit * 9 * Cin * Cout * (long long)sizeof(float);
     if (workspace) {
         VS_CHECK(workspace_bytes >= need, "vs_conv3x3_wgrad_tn: workspace of %lld bytes given, %lld needed", (long long)workspace_bytes, need);
@@ -1326,19 +1285,14 @@ extern "C" int vs_conv7x7_rgb_nhwc(const void *in_padded, const void *w, const f
     VS_CHECK((reinterpret_cast<uintptr_t>(w) & 15) == 0, "vs_conv7x7_rgb_nhwc: w must be 16-byte aligned");
     if (Nimg == 0) return 0;
     GemmArgs g;
-    g.A = in_padded; g.W = w; g.bias = bias; g.out = out; g.gate = nullptr; g.resid = nullptr;
+    g.A = in_padded; g.W = w; g.bias = bias; g.out = out;
     g.M = Nimg * H * W; g.N = Cout; g.K = 7 * 32;
     g.lda = 3; g.ldw = 8 * 32; g.ldo = Cout;
-    g.grp_in = g.M; g.grp_out = g.M; g.grp_off = 0;
-    g.gate_rows = g.M; g.gate_ld = Cout;
-    g.m_lo = 0;
-    g.a_grp_in = W; g.a_grp_out = Wp; g.a_grp_off = 0;  // pixel (row r, x) -> padded pixel r * Wp + x ...
+    g.grp_in = g.M; g.grp_out = g.M; g.gate_rows = g.M; g.gate_ld = Cout;
+    g.a_grp_in = W; g.a_grp_out = Wp;                   // pixel (row r, x) -> padded pixel r * Wp + x ...
     g.a_sup_in = H; g.a_sup_extra = (Hp - H) * Wp;      // ... plus the padding rows of the images before it
     g.a_kstride = Wp * 3;                               // next kernel row = next padded image row
-    g.ksplit = 1; g.ntaps = 0; g.tap_out_stride = 0; g.partials = nullptr; g.a_slice_stride = 0; g.w_slice_stride = 0; g.k_valid = 0; g.conv_H = 0; g.conv_W = 0;
-    g.rope_pos = nullptr; g.rope_kind = nullptr; g.rope_C = 0; g.rope_l2base = 0.f; g.rope_l2theta = 0.f; g.stagger = 0; g.row_band = wgrad_xcd(); g.acc_scale = 1.f; g.a_packed = 0; g.out_packed = 0; g.tap_on_a = 0;
-    static const int no256 = [] { const char *e = getenv("VS_STEM_NO256"); return e ? atoi(e) : 0; }();
-    if (Cout % 256 == 0 && g.M >= 256 && !no256) {
+    if (Cout % 256 == 0 && g.M >= 256) {
         const int nwg = vs::cdiv(g.M, 256) * (Cout / 256);
         if (dtype == 2) hipLaunchKernelGGL(conv7x7_256_kernel<1>, dim3(nwg), dim3(512), 0, stream, g);
         else hipLaunchKernelGGL(conv7x7_256_kernel<0>, dim3(nwg), dim3(512), 0, stream, g);
@@ -1364,17 +1318,14 @@ extern "C" int vs_conv7x7_rgb_split_nhwc(const float *in_padded, const void *wp,
     VS_CHECK((reinterpret_cast<uintptr_t>(wp) & 15) == 0 && (reinterpret_cast<uintptr_t>(in_padded) & 3) == 0, "vs_conv7x7_rgb_split_nhwc: alignment");
     if (Nimg == 0) return 0;
     GemmArgs g;
-    g.A = in_padded; g.W = wp; g.bias = bias; g.out = out; g.gate = nullptr; g.resid = nullptr;
+    g.A = in_padded; g.W = wp; g.bias = bias; g.out = out;
     g.M = Nimg * H * W; g.N = Cout; g.K = 8 * 64;         // (2-byte units of the f32 rows)
     g.lda = 6; g.ldw = 8 * 64; g.ldo = Cout;
-    g.grp_in = g.M; g.grp_out = g.M; g.grp_off = 0;
-    g.gate_rows = g.M; g.gate_ld = Cout;
-    g.m_lo = 0;
-    g.a_grp_in = W; g.a_grp_out = Wp; g.a_grp_off = 0;
+    g.grp_in = g.M; g.grp_out = g.M; g.gate_rows = g.M; g.gate_ld = Cout;
+    g.a_grp_in = W; g.a_grp_out = Wp;
     g.a_sup_in = H; g.a_sup_extra = (Hp - H) * Wp;
     g.a_kstride = Wp * 6;
-    g.ksplit = 1; g.ntaps = 0; g.tap_out_stride = 0; g.partials = nullptr; g.a_slice_stride = 0; g.w_slice_stride = 0; g.k_valid = 0; g.conv_H = 0; g.conv_W = 0;
-    g.rope_pos = nullptr; g.rope_kind = nullptr; g.rope_C = 0; g.rope_l2base = 0.f; g.rope_l2theta = 0.f; g.stagger = 0; g.row_band = wgrad_xcd(); g.acc_scale = acc_scale; g.a_packed = 0; g.out_packed = 0; g.tap_on_a = 0;
+    g.acc_scale = acc_scale;
     hipLaunchKernelGGL(conv7x7_256_kernel<kDtSplit>, dim3(vs::cdiv(g.M, 256) * (Cout / 256)), dim3(512), 0, stream, g);
     VS_HIP(hipGetLastError());
     return 0;
@@ -1396,17 +1347,15 @@ extern "C" int vs_conv7x7_rgb_split_up_nhwc(const float *in_padded, const void *
     VS_CHECK((reinterpret_cast<uintptr_t>(wp) & 15) == 0 && (reinterpret_cast<uintptr_t>(in_padded) & 3) == 0, "vs_conv7x7_rgb_split_up_nhwc: alignment");
     if (Nimg == 0) return 0;
     GemmArgs g;
-    g.A = in_padded; g.W = wp; g.bias = bias; g.out = out; g.gate = up_src; g.resid = nullptr;
+    g.A = in_padded; g.W = wp; g.bias = bias; g.out = out; g.gate = up_src;
     g.M = Nimg * H * W; g.N = Cout; g.K = 8 * 64;         // (2-byte units of the f32 rows)
     g.lda = 6; g.ldw = 8 * 64; g.ldo = Cout;
-    g.grp_in = g.M; g.grp_out = g.M; g.grp_off = 0;
-    g.gate_rows = g.M; g.gate_ld = Cout;
-    g.m_lo = 0;
-    g.a_grp_in = W; g.a_grp_out = Wp; g.a_grp_off = 0;
+    g.grp_in = g.M; g.grp_out = g.M; g.gate_rows = g.M; g.gate_ld = Cout;
+    g.a_grp_in = W; g.a_grp_out = Wp;
     g.a_sup_in = H; g.a_sup_extra = (Hp - H) * Wp;
     g.a_kstride = Wp * 6;
-    g.ksplit = 1; g.ntaps = 0; g.tap_out_stride = 0; g.partials = nullptr; g.a_slice_stride = 0; g.w_slice_stride = 0; g.k_valid = 0; g.conv_H = H / 2; g.conv_W = W / 2;
-    g.rope_pos = nullptr; g.rope_kind = nullptr; g.rope_C = 0; g.rope_l2base = 0.f; g.rope_l2theta = 0.f; g.stagger = 0; g.row_band = wgrad_xcd(); g.acc_scale = acc_scale; g.a_packed = 0; g.out_packed = 0; g.tap_on_a = 0;
+    g.acc_scale = acc_scale;
+    g.conv_H = H / 2; g.conv_W = W / 2;
     hipLaunchKernelGGL((conv7x7_256_kernel<kDtSplit, true>), dim3(vs::cdiv(g.M, 256) * (Cout / 256)), dim3(512), 0, stream, g);
     VS_HIP(hipGetLastError());
     return 0;

@@ -508,19 +508,8 @@ __global__ void __launch_bounds__(512, 1) gemm256_kernel(const GemmArgs g) {
         const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, idx = bid / 8;
         bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
     }
-    int tm = bid / tiles_n, tn = bid % tiles_n;
-    if (g.row_band > 0 && tiles_n > 4) {
-        // bands of row_band row tiles, column tile slowest inside a band: the ~32 workgroups an XCD runs at a time then cover row_band row
-        // tiles x (32 / row_band) column tiles instead of 2 x 16 -- fewer distinct W panels in flight per XCD, each A panel shared less
-        const int per_band = g.row_band * tiles_n, band = bid / per_band, rows = min(g.row_band, tiles_m - band * g.row_band);
-        const int r = bid - band * per_band;
-        tn = r / rows; tm = band * g.row_band + (r - tn * rows);
-    }
+    const int tm = bid / tiles_n, tn = bid % tiles_n;
     const int m0 = g.m_lo + tm * BM2, n0 = tn * BN2;
-    if (g.stagger > 0 && blockIdx.x < 256) {
-        const int n = (int)((blockIdx.x >> 3) & 7) * g.stagger;
-        for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(127);
-    }
 
     const unsigned short *A = reinterpret_cast<const unsigned short *>(g.A);
     const unsigned short *W = reinterpret_cast<const unsigned short *>(g.W);
@@ -547,11 +536,10 @@ __global__ void __launch_bounds__(512, 1) gemm256_kernel(const GemmArgs g) {
 // Logical workgroup id of the split-K / tap-fused kernels.  The hardware hands consecutive blockIdx.x to consecutive XCDs (8 on MI355X, each
 // with its own 4 MB L2), so "tile fastest inside a K slice" put the workgroups that read the same rows of A and W on EIGHT different L2s:
 // the counters showed the split-class weight gradients fetching 151 GB (linears) + 122 GB (3x3 convolutions) per 8-scene training step for
-// ~55 GB of operands, at 4-5.5 TB/s.  With g.row_band != 0 (the weight-gradient entries set it: VS_WGRAD_XCD, default 1) consecutive LOGICAL
-// ids share an XCD (gemm256_kernel's remap): the nine taps / the tiles of one K slice meet in one L2.
-__device__ __forceinline__ int splitk_logical_block(const GemmArgs &g) {
+// ~55 GB of operands, at 4-5.5 TB/s.  Consecutive LOGICAL ids share an XCD (gemm256_kernel's remap): the nine taps / the tiles of one K slice
+// meet in one L2.
+__device__ __forceinline__ int splitk_logical_block() {
     const int b = blockIdx.x;
-    if (g.row_band == 0) return b;
     const int n = gridDim.x, q = n >> 3, r = n & 7, xcd = b & 7, idx = b >> 3;
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
@@ -571,7 +559,7 @@ __global__ void __launch_bounds__(512, 1) gemm256_splitk_kernel(const GemmArgs g
     const int tiles_n = (g.N + BN2 - 1) / BN2;
     const int tiles = ((g.M + BM2 - 1) / BM2) * tiles_n;
     const int ntaps = g.ntaps > 0 ? g.ntaps : 1;
-    const int lb = splitk_logical_block(g);
+    const int lb = splitk_logical_block();
     const int ksp = lb / (tiles * ntaps);
     const int rem = lb - ksp * tiles * ntaps;
     const int tap = rem / tiles, bid = rem - tap * tiles;
@@ -640,7 +628,7 @@ __global__ void __launch_bounds__(512, 1) gemm256_tn_splitk_kernel(const GemmArg
     const int wr = wid >> 2, wc = wid & 3;
     const int tiles_n = (g.N + BN2 - 1) / BN2;
     const int tiles = ((g.M + BM2 - 1) / BM2) * tiles_n;
-    const int lb = splitk_logical_block(g);
+    const int lb = splitk_logical_block();
     const int ksp = lb / tiles;
     const int bid = lb - ksp * tiles;
     const int tm = bid / tiles_n, tn = bid % tiles_n;
@@ -710,7 +698,7 @@ __global__ void __launch_bounds__(512, 1) gemm256_split_atn_splitk_kernel(const 
     const int wr = wid >> 2, wc = wid & 3;
     const int tiles_n = (g.N + BN2 - 1) / BN2;
     const int tiles = ((g.M + BM2 - 1) / BM2) * tiles_n;
-    const int lb = splitk_logical_block(g);
+    const int lb = splitk_logical_block();
     const int ksp = lb / tiles;
     const int bid = lb - ksp * tiles;
     const int tm = bid / tiles_n, tn = bid % tiles_n;
@@ -797,7 +785,7 @@ __global__ void __launch_bounds__(512, 1) conv3x3_wgrad_split_atn_kernel(const G
     const int wr = wid >> 2, wc = wid & 3;
     const int tiles_n = g.N / BN2;
     const int tiles = (g.M / BM2) * tiles_n;
-    const int lb = splitk_logical_block(g);
+    const int lb = splitk_logical_block();
     const int ksp = lb / (tiles * 9);
     const int rem = lb - ksp * tiles * 9;
     const int tap = rem / tiles, bid = rem - tap * tiles;
@@ -899,7 +887,7 @@ __global__ void __launch_bounds__(512, 1) conv3x3_wgrad_tn_kernel(const GemmArgs
     const int ngroups = (9 + G - 1) / G;
     const int tiles_n = (g.N + BN2 - 1) / BN2;
     const int tiles = (G > 1 ? 1 : (Cin + BM2 - 1) / BM2) * tiles_n;
-    const int lb = splitk_logical_block(g);
+    const int lb = splitk_logical_block();
     const int ksp = lb / (tiles * ngroups);        // (k-slice, tap group, tile): the taps of a slice share X and dY through L2
     const int rem = lb - ksp * tiles * ngroups;
     const int grp = rem / tiles, bid = rem - grp * tiles;

@@ -13,54 +13,53 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 
 constexpr int BN = 128;  // BM = 32*MI (MI = 16-row fragments per wave in M: 4 -> 128 rows, 8 -> 256 rows)
 
+// Default member values describe a plain GEMM (no tail, window, taps, K slices, RoPE or packed operands): each entry point sets the rest.
 struct GemmArgs {
-    const void *A;
-    const void *W;
-    const float *bias;
-    void *out;
-    const float *gate;
-    const float *resid;  // epilogue 2: source of the residual stream (same row layout as out); null = out itself (in-place update)
-    int M, N, K;
-    int lda, ldw, ldo;
-    int grp_in, grp_out, grp_off;
-    int gate_rows;  // rows of A per gate vector
-    int gate_ld;
-    int m_lo;  // first logical row this launch covers (rows [m_lo, M)); tail launches of a split GEMM start past 0
-    int a_grp_in, a_grp_out, a_grp_off;  // INPUT row map: A row of m = (m / a_grp_in) * a_grp_out + a_grp_off + m % a_grp_in
+    const void *A = nullptr;
+    const void *W = nullptr;
+    const float *bias = nullptr;
+    void *out = nullptr;
+    const float *gate = nullptr;
+    const float *resid = nullptr;  // epilogue 2: source of the residual stream (same row layout as out); null = out itself (in-place update)
+    int M = 0, N = 0, K = 0;
+    int lda = 0, ldw = 0, ldo = 0;
+    int grp_in = 0, grp_out = 0, grp_off = 0;
+    int gate_rows = 0;  // rows of A per gate vector
+    int gate_ld = 0;
+    int m_lo = 0;  // first logical row this launch covers (rows [m_lo, M)); tail launches of a split GEMM start past 0
+    int a_grp_in = 0, a_grp_out = 0, a_grp_off = 0;  // INPUT row map: A row of m = (m / a_grp_in) * a_grp_out + a_grp_off + m % a_grp_in
     // window-GEMM extras (7x7 RGB stem, gemm_kernel only): every a_sup_in row groups skip a_sup_extra more A rows (image
     // padding rows), and k-step kt reads its 32-wide slice at element offset kt * a_kstride (next image row), not kt * 32
-    int a_sup_in, a_sup_extra, a_kstride;
+    int a_sup_in = 0x7fffffff, a_sup_extra = 0, a_kstride = 32;
     // tap-fused weight gradient (gemm_kernel, epilogue 2): ntaps > 0 -> the launch is ntaps GEMMs sharing A; tap t reads the
     // W operand shifted by tap_shift[t] elements and adds into out + t * tap_out_stride; workgroup order is (k-slice, tap, tile)
     // so that the taps of one K slice run together and their re-reads of A / X hit the caches instead of HBM
-    int ntaps;
-    long long tap_out_stride;
-    int tap_shift[9];
-    int ksplit;  // > 1 (epilogue 2 only): blockIdx.y-th of ksplit equal K ranges, summed into out with f32 atomics
+    int ntaps = 0;
+    long long tap_out_stride = 0;
+    int tap_shift[9] = {};
+    int ksplit = 1;  // > 1 (epilogue 2 only): blockIdx.y-th of ksplit equal K ranges, summed into out with f32 atomics
     // weight-gradient launches with a workspace: K slice s (tap t) STORES its partial tile to partials[((s * ntaps + t) * M + m) * N + n]
     // (plain coalesced stores; splitk_reduce_kernel sums the slices) instead of meeting the other slices through atomics --
     // f32 atomics sustain only ~0.3 TB/s on this part, a tenth of the plain store rate.  The kernels then run the epilogue with
     // ksplit = -1 ("store").
-    float *partials;
+    float *partials = nullptr;
     // element offset of K slice s within A / W: s * a_slice_stride (0: the slices are consecutive column ranges of one matrix,
     // i.e. K / ksplit).  Weight-gradient operands are stored slice-blocked, [slice][channel][slice length], so that the rows a
     // workgroup walks are a few KB apart instead of the whole reduction length (4 M pixels = 8 MB: one TLB entry per row and
     // K step otherwise)
-    long long a_slice_stride, w_slice_stride;
-    int k_valid;  // reduction-major (TN) weight gradient: real number of reduction rows; rows in [k_valid, K) read as zeros
-    int conv_H, conv_W;  // reduction-major 3x3-conv weight gradient: image size (reduction row = pixel n*H*W + y*W + x of an NHWC tensor)
+    long long a_slice_stride = 0, w_slice_stride = 0;
+    int k_valid = 0;  // reduction-major (TN) weight gradient: real number of reduction rows; rows in [k_valid, K) read as zeros
+    int conv_H = 0, conv_W = 0;  // reduction-major 3x3-conv weight gradient: image size (reduction row = pixel n*H*W + y*W + x of an NHWC tensor)
     // epilogue 4 (STORE16 + RoPE on the q and k column blocks of a packed qkv projection, head_dim 64): per OUTPUT row
     // pos[2] and kind (0: 2-D pairs (i, i+16) per 32-half with pos[0]/pos[1], 1: 1-D interleaved pairs with pos[0], 2: none)
-    const int32_t *rope_pos;
-    const uint8_t *rope_kind;
-    int rope_C;  // columns [0, C) = q, [C, 2C) = k, rest untouched
-    float rope_l2base, rope_l2theta;  // log2 of the 2-D base / 1-D theta
-    int stagger;  // experiment: first-round workgroups of gemm256_kernel sleep (bid % 8) * stagger * ~4 us before starting
-    int row_band; // gemm256_kernel: > 0 = tiles are walked in bands of row_band row tiles, column tile slowest inside a band (L2: see gemm256_kernel)
-    int tap_on_a;     // tap-fused weight gradient: the tap shift moves the A operand instead of W (split class: a packed W cannot be shifted)
-    int out_packed;   // split operands, epilogues 0 / 1 / 3: the output is written in the packed (hi, lo) form (the A operand of the next GEMM)
-    int a_packed;     // split operands: A is ALREADY in the packed (hi, lo) form of vs_split_pack_weight (scale 2^0): the kernels skip the conversion
-    float acc_scale;  // split operands (kDtSplit): the packed weights carry a power-of-two scale 2^e; the epilogue multiplies the accumulators by 2^-e
+    const int32_t *rope_pos = nullptr;
+    const uint8_t *rope_kind = nullptr;
+    int rope_C = 0;  // columns [0, C) = q, [C, 2C) = k, rest untouched
+    float rope_l2base = 0.f, rope_l2theta = 0.f;  // log2 of the 2-D base / 1-D theta
+    int tap_on_a = 0;     // tap-fused weight gradient: the tap shift moves the A operand instead of W (split class: a packed W cannot be shifted)
+    int out_packed = 0;   // split operands, epilogues 0 / 1 / 3: the output is written in the packed (hi, lo) form (the A operand of the next GEMM)
+    int a_packed = 0;     // split operands: A is ALREADY in the packed (hi, lo) form of vs_split_pack_weight (scale 2^0): the kernels skip the conversion
+    float acc_scale = 1.f;  // split operands (kDtSplit): the packed weights carry a power-of-two scale 2^e; the epilogue multiplies the accumulators by 2^-e
 };
 
 // Operand dtype of the MFMA kernels (template parameter `BF16` of every kernel below: the name predates the third value).

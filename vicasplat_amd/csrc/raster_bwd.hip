@@ -15,8 +15,6 @@
 //        block-reduced atomic for the per-camera twist gradient dL/dtau = (rho, theta), T_cw' = Exp(tau) T_cw.
 #include "common.h"
 
-#include <cstdlib>
-
 namespace {
 
 using vs::kGeomFloats;
@@ -909,14 +907,10 @@ extern "C" int vs_raster_backward(const VsRasterIn *in, const VsRasterOut *saved
     if (g->dL_dtau) VS_HIP(hipMemsetAsync(g->dL_dtau, 0, (size_t)C * 6 * sizeof(float), stream));
     if (g->dL_dmeans2D) VS_HIP(hipMemsetAsync(g->dL_dmeans2D, 0, (size_t)C * P * 2 * sizeof(float), stream));
     if (saved->num_rendered > 0) {
-        // one wave per tile (lane = 2x2 block) when there are enough tiles to fill the chip with single waves, as the forward's render
-        // kernel; four waves per tile (a quadrant each) for small calls.  VS_RBWD_WAVES = 1 | 4 forces one (read per call: the tests run both).
-        const char *fw = getenv("VS_RBWD_WAVES");
-        const float *ckpt = (const float *)saved->buffers[VS_BUF_CHECKPOINT];
         // segment-parallel replay whenever the forward saved checkpoints (every differentiated call of this package); the whole-list kernel
-        // (four waves per tile) for a caller without VS_RASTER_SAVE_FOR_BACKWARD.  VS_RBWD_WAVES=4 forces the latter (read per call: tests).
-        const bool seg = ckpt && !(fw && atoi(fw) == 4);
-        if (seg) {
+        // (four waves per tile) for a caller without VS_RASTER_SAVE_FOR_BACKWARD
+        const float *ckpt = (const float *)saved->buffers[VS_BUF_CHECKPOINT];
+        if (ckpt) {
             VS_CHECK(saved->color && (!g->dL_ddepth || saved->depth), "vs_raster_backward: the checkpoint route reads the rendered colour / depth of the forward");
             const size_t ck_slots = (size_t)(saved->num_rendered >> vs::kCkShift) + (size_t)tiles * C;
             const int2 *cktab = reinterpret_cast<const int2 *>(ckpt + ck_slots * vs::kCkFloats);

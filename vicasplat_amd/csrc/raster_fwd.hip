@@ -17,8 +17,6 @@
 // radii / tile ranges / sorted ids are bit-identical to the CPU oracle.
 #include "common.h"
 
-#include <cstdlib>
-
 namespace {
 
 using vs::kGeomFloats;
@@ -878,14 +876,18 @@ segment_sort_kernel(const int2 *__restrict__ segs, int nslots, const unsigned lo
 // staged record's footprint test is read from LDS once per tile instead of once per quadrant-wave, the batch barriers are wave-local, and
 // a tile occupies one wave slot (12 tiles per CU by LDS instead of 3-4 workgroups of four waves).  Same arithmetic, same order per pixel:
 // bit-identical output (tests/test_raster_gpu.py runs both).  Measured: see DESIGN 5.
-template <bool COUNT_TOUCHED, int NW, int NTB = 256>
+template <bool COUNT_TOUCHED, int NW>
 __global__ void __launch_bounds__(64 * NW)
 render_kernel(int P, int W, int H, const int2 *__restrict__ ranges, const uint32_t *__restrict__ point_list,
               const float *__restrict__ geom, const float *__restrict__ background, float *__restrict__ out_color,
               float *__restrict__ out_depth, float *__restrict__ out_opacity, float *__restrict__ final_T,
               int32_t *__restrict__ n_contrib, int32_t *__restrict__ n_touched, float *__restrict__ ckpt, int2 *__restrict__ cktab) {
-    constexpr int NTHR = 64 * NW, NT = NTB, RPT = NT / NTHR, NQ = 4 / NW;   // staged batch: NT records, RPT per thread; NQ quadrants per wave
-    static_assert(vs::kCkSeg % NTB == 0, "checkpoints fall on batch boundaries");
+    // staged batch: NT records, RPT per thread; NQ quadrants per wave.  One wave per tile stages batches of 64 (round 5: 96 VGPRs and 3.3 KiB
+    // of LDS per wave -> five waves per SIMD instead of three; the kernel is latency bound -- PMC: VALU issue 0.42, 38 % of the wave cycles
+    // waiting -- and a batch is one round of the 64-entry footprint test anyway.  256 / 128 / 64: 5.23 / 4.73 / 4.60 ms on the bench step,
+    // bit-identical)
+    constexpr int NTHR = 64 * NW, NT = NW == 1 ? 64 : 256, RPT = NT / NTHR, NQ = 4 / NW;
+    static_assert(vs::kCkSeg % NT == 0, "checkpoints fall on batch boundaries");
     __shared__ float4 sq0[NT], sq1[NT], sq2[NT];
     __shared__ uint32_t sid[NT];
     const int gx = (W + kTile - 1) / kTile;
@@ -1173,28 +1175,14 @@ extern "C" int64_t vs_raster_forward(const VsRasterIn *in, VsRasterOut *out, VsA
     dim3 rgrid(tiles, C);
     // One wave per tile when there are enough tiles to fill the chip with single waves (>= 16 per CU: the batched bench / training calls),
     // four waves per tile (a quadrant each) for small calls, where a tile's latency matters more than wave slots.  Same results either
-    // way (bit-identical); VS_RENDER_WAVES=1 | 4 forces one (A/B: DESIGN 5 -- 5.14 vs 5.20 ms on the 288-view bench step).
-    static const int force_waves = [] { const char *e = getenv("VS_RENDER_WAVES"); return e ? atoi(e) : 0; }();
-    const int render_waves = force_waves ? force_waves : ((long long)tiles * C >= 4096 ? 1 : 4);
-#define VS_RENDER(CNT_, NW_)                                                                                                         \
-    hipLaunchKernelGGL((render_kernel<CNT_, NW_>), rgrid, dim3(64 * NW_), 0, stream, P, W, H, ranges, point_list, geom, in->background, \
-                       out->color, out->depth, out->opacity, final_T, n_contrib, out->n_touched, ckpt, cktab)
-    // one wave per tile: staged batches of 64 records (round 5: 96 VGPRs and 3.3 KiB of LDS per wave -> five waves per SIMD instead of
-    // three; the kernel is latency bound -- PMC: VALU issue 0.42, 38 % of the wave cycles waiting -- and a batch is one round of the
-    // 64-entry footprint test anyway.  256 / 128 / 64: 5.23 / 4.73 / 4.60 ms on the bench step, bit-identical; VS_RENDER_NT = 256 | 128 for A/B)
-    static const int ntb = [] { const char *e = getenv("VS_RENDER_NT"); return e ? atoi(e) : 64; }();
-#define VS_RENDER1(CNT_, NT_)                                                                                                         \
-    hipLaunchKernelGGL((render_kernel<CNT_, 1, NT_>), rgrid, dim3(64), 0, stream, P, W, H, ranges, point_list, geom, in->background,   \
-                       out->color, out->depth, out->opacity, final_T, n_contrib, out->n_touched, ckpt, cktab)
+    // way (bit-identical; DESIGN 5 -- 5.14 vs 5.20 ms on the 288-view bench step).
     // (round 6, measured and not kept: lane = one 2x2 pixel block of the tile -- the mapping of the backward's replay kernels, a trip serving 64
     // (block, entry) pairs instead of 16, record reads and mask bookkeeping paid once per four pixels: 4.45 vs 4.35 ms per 288 views, identical
     // images.  The forward's trips are not what bounds it.)
-    if (render_waves == 1) {
-        if (ntb == 256) { if (count) VS_RENDER1(true, 256); else VS_RENDER1(false, 256); }
-        else if (ntb == 128) { if (count) VS_RENDER1(true, 128); else VS_RENDER1(false, 128); }
-        else { if (count) VS_RENDER1(true, 64); else VS_RENDER1(false, 64); }
-    }
-#undef VS_RENDER1
+#define VS_RENDER(CNT_, NW_)                                                                                                         \
+    hipLaunchKernelGGL((render_kernel<CNT_, NW_>), rgrid, dim3(64 * NW_), 0, stream, P, W, H, ranges, point_list, geom, in->background, \
+                       out->color, out->depth, out->opacity, final_T, n_contrib, out->n_touched, ckpt, cktab)
+    if ((long long)tiles * C >= 4096) { if (count) VS_RENDER(true, 1); else VS_RENDER(false, 1); }
     else { if (count) VS_RENDER(true, 4); else VS_RENDER(false, 4); }
 #undef VS_RENDER
     VS_HIP(hipGetLastError());

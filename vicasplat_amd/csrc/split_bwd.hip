@@ -122,17 +122,16 @@ transpose_f32_kernel(const float *__restrict__ in, long long ld_in, void *__rest
 // thread (rows {4g..4g+3, 16+4g..16+4g+3} of a 32-row block: 8 LDS reads -> one 16-byte hi store + one 16-byte lo store; four lanes fill
 // the 64 + 64 bytes of a block), LDS rows of 66 words (the chunk reads of 32 lanes fall into 32 different banks), the bias gradient summed
 // from the registers of the load phase (two DPP steps + one LDS row per wave) instead of a second walk over the tile.
-// RFAST: consecutive workgroups walk DOWN the rows of one 64-column band (their stores extend the same output rows).
-template <int TR, bool RFAST>
+template <int TR>
 __global__ void __launch_bounds__(256)
 transpose_pack_plain_kernel(const float *__restrict__ in, long long ld_in, unsigned short *__restrict__ out, long long ld_out, int R, int C, int Rpad,
                             int relu, float scale, float *__restrict__ colsum) {
     constexpr int S = 66;
     __shared__ float t[TR][S];
     __shared__ float cs[4][64];
-    const int tiles_c = C >> 6, tiles_r = Rpad / TR;
-    const int r0 = (RFAST ? (int)(blockIdx.x % tiles_r) : (int)(blockIdx.x / tiles_c)) * TR;
-    const int c0 = (RFAST ? (int)(blockIdx.x / tiles_r) : (int)(blockIdx.x % tiles_c)) * 64;
+    const int tiles_c = C >> 6;
+    const int r0 = (int)(blockIdx.x / tiles_c) * TR;
+    const int c0 = (int)(blockIdx.x % tiles_c) * 64;
     const int c4 = (threadIdx.x & 15) * 4;
     float4 v[TR / 16];
 #pragma unroll
@@ -321,24 +320,16 @@ int transpose_f32_entry(const char *fn, bool pack, const float *in, int64_t ld_i
     VS_CHECK(nblk <= 0x7fffffffLL, "%s: too many tiles", fn);
     dim3 grid((unsigned)nblk), block(256);
     const float scale = ldexpf(1.0f, scale_exp);
-    // plain packing transposes (every linear / 1x1 weight gradient's dY^T) take the chunk-store kernel; VS_TP_PLAIN = 0 / 64 / 128 / 256 (rows per
-    // tile) and VS_TP_RFAST for the A/B
+    // plain packing transposes (every linear / 1x1 weight gradient's dY^T) take the chunk-store kernel: 128 rows per tile, 64 when Rpad is
+    // not a multiple of 128
     if (pack && cH == 0 && C % 64 == 0 && ld_in % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0) {
-        const char *e = getenv("VS_TP_PLAIN"), *e2 = getenv("VS_TP_RFAST");
-        int tr = e ? atoi(e) : 128;
-        const bool rfast = e2 ? atoi(e2) != 0 : false;
-        while (tr > 64 && Rpad % tr != 0) tr >>= 1;
-        if (tr == 64 || tr == 128 || tr == 256) {
-            dim3 g2((unsigned)((long long)(C / 64) * (Rpad / tr)));
-            unsigned short *o16 = reinterpret_cast<unsigned short *>(out);
-#define VS_TP(TR_, RF_) hipLaunchKernelGGL((transpose_pack_plain_kernel<TR_, RF_>), g2, block, 0, stream, in, (long long)ld_in, o16, (long long)ld_out, R, C, Rpad, relu, scale, colsum)
-            if (tr == 64) { if (rfast) VS_TP(64, true); else VS_TP(64, false); }
-            else if (tr == 128) { if (rfast) VS_TP(128, true); else VS_TP(128, false); }
-            else { if (rfast) VS_TP(256, true); else VS_TP(256, false); }
-#undef VS_TP
-            VS_HIP(hipGetLastError());
-            return 0;
-        }
+        const int tr = Rpad % 128 == 0 ? 128 : 64;
+        dim3 g2((unsigned)((long long)(C / 64) * (Rpad / tr)));
+        unsigned short *o16 = reinterpret_cast<unsigned short *>(out);
+        if (tr == 128) hipLaunchKernelGGL(transpose_pack_plain_kernel<128>, g2, block, 0, stream, in, (long long)ld_in, o16, (long long)ld_out, R, C, Rpad, relu, scale, colsum);
+        else hipLaunchKernelGGL(transpose_pack_plain_kernel<64>, g2, block, 0, stream, in, (long long)ld_in, o16, (long long)ld_out, R, C, Rpad, relu, scale, colsum);
+        VS_HIP(hipGetLastError());
+        return 0;
     }
     if (pack) hipLaunchKernelGGL(transpose_f32_kernel<true>, grid, block, 0, stream, in, (long long)ld_in, out, (long long)ld_out, R, C, relu, cH, cW, dy, dx, scale, colsum);
     else hipLaunchKernelGGL(transpose_f32_kernel<false>, grid, block, 0, stream, in, (long long)ld_in, out, (long long)ld_out, R, C, relu, cH, cW, dy, dx, scale, colsum);

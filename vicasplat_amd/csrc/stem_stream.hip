@@ -14,8 +14,6 @@
 #include "common.h"
 #include "gemm_common.h"
 
-#include <cstdlib>
-
 namespace {
 
 struct StemStreamArgs {
@@ -32,8 +30,8 @@ constexpr int kIP = 96;                 // byte pitch of one ring row of one (co
 constexpr int kIS = 16 * kIP;           // one (copy, channel) image: 16 ring slots (two batches of 8 rows)
 constexpr int kImgBytes = 2 * 4 * 3 * kIS;   // (hi | lo) x 4 shifted copies x 3 channels
 
-template <int PT>     // 16-pixel tiles per step: the strip is 16 * PT pixels wide
 __global__ void __launch_bounds__(512) stem_up_stream_kernel(const StemStreamArgs a) {
+    constexpr int PT = 2;     // 16-pixel tiles per step: the strip is 16 * PT pixels wide
     __shared__ __attribute__((aligned(16))) unsigned char sImg[kImgBytes];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -170,8 +168,8 @@ __global__ void __launch_bounds__(512) stem_up_stream_kernel(const StemStreamArg
                 // ---- software pipeline: the bilinear taps of the NEXT tile are requested before this tile's MFMAs (8 x 16 bytes per lane in flight
                 // for a whole tile time; requested and consumed inside one tile they cost 2.1 of 6.6 ms, and every wait for them also waited for
                 // the previous tile's stores: vmcnt counts in order) ----
-                float4 (&tc)[2][4] = ((PT * 0 + pt) & 1) ? tpB : tpA;      // this tile's taps
-                float4 (&tn)[2][4] = ((PT * 0 + pt) & 1) ? tpA : tpB;      // the next tile's
+                float4 (&tc)[2][4] = (pt & 1) ? tpB : tpA;      // this tile's taps
+                float4 (&tn)[2][4] = (pt & 1) ? tpA : tpB;      // the next tile's
                 // (source rows that do not change from one output row to the next leave both tiles' taps where they are: half the gathers)
                 if (pt + 1 < PT) { if (!same_prev) load_taps(tn, r0, r1, pt + 1); }
                 else if (yo + 1 < a.H && !same_next) load_taps(tn, r0_n, r1_n, 0);
@@ -207,12 +205,6 @@ __global__ void __launch_bounds__(512) stem_up_stream_kernel(const StemStreamArg
                 float *rowp = a.out + ((long long)(n * a.H + yo) * a.W + x0s + pt * 16 + l16) * C;
                 store_split8(rowp, chb + 4 * g, v[0], v[1]);
             }
-            if (PT == 1 && !same_next) {      // (one tile per row: the next row's taps were loaded into the second buffer)
-#pragma unroll
-                for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) tpA[ct][k] = tpB[ct][k];
-            }
             r0 = r0_n; r1 = r1_n; same_prev = same_next;
             ly_c = sy_n - (float)y0_n;
         }
@@ -234,9 +226,7 @@ extern "C" int vs_stem7x7_up_split_stream(const float *img_padded, const float *
     a.img = img_padded; a.w = w; a.bias = bias; a.trunk = trunk; a.out = (float *)out;
     a.N = N; a.H = H; a.W = W; a.Hp = Hp; a.Wp = Wp;
     a.w_scale = ldexpf(1.f, w_scale_exp); a.inv_scale = ldexpf(1.f, -w_scale_exp);
-    static const int pt = [] { const char *e = getenv("VS_STEM_PT"); return e ? atoi(e) : 2; }();
-    if (pt == 1) hipLaunchKernelGGL(stem_up_stream_kernel<1>, dim3((unsigned)nwg), dim3(512), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(stem_up_stream_kernel<2>, dim3((unsigned)nwg), dim3(512), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(stem_up_stream_kernel, dim3((unsigned)nwg), dim3(512), 0, (hipStream_t)stream, a);
     VS_HIP(hipGetLastError());
     return 0;
 }

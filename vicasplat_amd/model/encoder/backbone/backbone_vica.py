@@ -23,12 +23,8 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-import os
-
 from .... import ops
 
-# A/B switch of the packed q | k | v route of the split class (VS_ATTN_PACKED=0: f32 q | k | v + attention_split_kernel, the round-3 path)
-_ATTN_PACKED = os.environ.get("VS_ATTN_PACKED", "1") != "0"
 
 
 class _Mlp(nn.Module):
@@ -256,7 +252,7 @@ class VicaNet(nn.Module):
         act = (lambda r, c: ops.split_act(r, c, dev)) if self.split else (lambda r, c: torch.empty(r, c, **f16))
         # split class, round 4: q | k | v leave the projection's RoPE epilogue in the packed (hi, lo) form as well and the attention kernel
         # stages them by LDS-DMA without converting anything (ops.attention on int32 slices -> attention_sp_kernel)
-        qkv_packed = self.split and _ATTN_PACKED
+        qkv_packed = self.split
         qact = act if qkv_packed else (lambda r, c: torch.empty(r, c, **f16))
         cols3 = lambda t, C_: ((t.data if qkv_packed else t)[:, :C_], (t.data if qkv_packed else t)[:, C_:2 * C_], (t.data if qkv_packed else t)[:, 2 * C_:])
         h = act(BT * N, Ce)

@@ -12,13 +12,8 @@ import torch
 import torch.nn.functional as F      # F.pad / F.unfold of the exact-f32 class's im2col stem only -- no torch convolution / interpolation anywhere
 from torch import nn
 
-import os
-
 from .... import ops
 
-_PTS_UP_PACKED = os.environ.get("VS_PTS_UP_PACKED", "1") != "0"     # A/B switch: 0 = f32 upsampled map into the pts3d head's fused conv (round 3)
-_STEM_STREAM = os.environ.get("VS_STEM_STREAM", "1") != "0"       # A/B switch: 0 = the tile route of the fused stem (round 4)
-_STEM_UP_FUSED = os.environ.get("VS_STEM_UP_FUSED", "1") != "0"   # A/B switch: 0 = stem -> f32 map -> upsample-add kernel (round 3)
 
 
 def _no_torch_forward(self, *a, **k):
@@ -248,11 +243,11 @@ class PixelwiseTaskWithDPT(nn.Module):
         """-> [BT,C,H,W] view (channels-last memory, pixel stride 4) of the head output in the compute dtype, BEFORE the 'exp' post-process;
         C = 3 (xyz), or 4 with the confidence channel (predict_conf: the same fused kernels, whose fourth output column was zero padding)."""
         nc = self.num_channels
-        pk = _PTS_UP_PACKED and self.split and self.dpt.head[0].out_channels == 128 and self.dpt.head[0].in_channels in (64, 128, 256)
+        pk = self.split and self.dpt.head[0].out_channels == 128 and self.dpt.head[0].in_channels in (64, 128, 256)
         x, P = self._trunk(tokens, gh, gw, packed_out=pk and (tokens[self.dpt.hooks[0]].shape[0] * 64 * gh * gw) >= 224 * 256)
         x = ops.conv3x3_nhwc(x, P["h0.w"], P["h0.b"])
         npix = x.shape[0] * 4 * x.shape[1] * x.shape[2]
-        if _PTS_UP_PACKED and self.split and npix % 256 == 0 and x.shape[-1] == 128 and self.dpt.head[2].out_channels == 128:
+        if self.split and npix % 256 == 0 and x.shape[-1] == 128 and self.dpt.head[2].out_channels == 128:
             # round 4: the upsampled 256^2 x 128 map is written PACKED (hi, lo) by the bilinear kernel (same bytes) and the fused conv3 -> ReLU ->
             # dot head reads it without converting (conv3x3_256x128_split_kernel<., ., A_PACKED>)
             if "h4f32.w" not in P:
@@ -307,11 +302,11 @@ class PixelwiseTaskWithDPT(nn.Module):
                 c7 = self.dpt.input_merger[0]
                 P["stem.ws7"], P["stem.b"] = ops.pack_conv7x7_rgb_weight(c7.weight, "split"), c7.bias.detach().float().contiguous()
             H_, W_ = frames.shape[-2], frames.shape[-1]
-            if (_STEM_UP_FUSED and fuse_gs and x.shape[-1] == d.input_merger[0].out_channels and x.is_contiguous()
+            if (fuse_gs and x.shape[-1] == d.input_merger[0].out_channels and x.is_contiguous()
                     and (2 * x.shape[1], 2 * x.shape[2]) == (H_, W_)):
                 # round 4: up2(trunk) + relu(stem) leaves the STEM kernel's epilogue in the packed form -- the f32 stem map (12.9 GB written and
                 # read back per 24-scene step) and the stand-alone upsample-add launch are gone
-                if _STEM_STREAM and W_ % 32 == 0 and d.input_merger[0].out_channels == 256:
+                if W_ % 32 == 0 and d.input_merger[0].out_channels == 256:
                     # round 5: the streaming form (csrc/stem_stream.hip): the image as an LDS ring, taps by transpose reads, 9.4 -> see DESIGN
                     if "stem.w32" not in P:
                         c7 = d.input_merger[0]

@@ -11,8 +11,6 @@ First version of the training path: correct and kernel-backed
 """
 from __future__ import annotations
 
-import os
-
 import torch
 import torch.nn.functional as F
 import torch.utils.checkpoint
@@ -21,8 +19,6 @@ from ... import autograd as A
 from ... import ops
 
 LN_EPS = 1e-6
-_IM2COL = os.environ.get("VS_IM2COL", "1") != "0"            # 0: F.unfold + F.pad rows of the training stem (A/B runs)
-_HEAD_TAIL = os.environ.get("VS_HEAD_TAIL", "1") != "0"      # 0: the operator-by-operator backward of the heads' last 1x1 convolution (A/B runs)
 
 
 def _ln_f32(P, name, x):
@@ -83,8 +79,6 @@ def forward_train(model, image: torch.Tensor, intrinsics: torch.Tensor, dt=torch
         cb = auto_checkpoint_blocks(image.shape[0], image.shape[1] * image.shape[3] * image.shape[4] / (8.0 * 65536.0),
                                     torch.cuda.get_device_properties(image.device).total_memory / 2 ** 30, model.backbone.config.enc_depth,
                                     model.backbone.config.dec_depth, half=dt != A.SPLIT)
-    if os.environ.get("VS_CKPT_BLOCKS"):                  # "n_enc,n_dec": experiment override of the policy
-        cb = tuple(int(v) for v in os.environ["VS_CKPT_BLOCKS"].split(","))
     ck_enc = lambda i: ckpt and (cb is None or i < cb[0])
     ck_dec = lambda i: ckpt and (cb is None or i < cb[1])
     lin = lambda name, x: A.linear(x, P[name + ".weight"], P.get(name + ".bias"), dt)
@@ -182,7 +176,7 @@ def forward_train(model, image: torch.Tensor, intrinsics: torch.Tensor, dt=torch
 
     def conv1x1_tail(name, t):              # the head's last 1x1 convolution behind a ReLU: one fused backward pass (csrc/head_bwd.hip)
         w = P[name + ".weight"].flatten(1)
-        if _HEAD_TAIL and A.head_tail_ok(t, w) and t.dtype == adt:
+        if A.head_tail_ok(t, w) and t.dtype == adt:
             return A.head_tail(t, w, P.get(name + ".bias"), dt)
         return conv1x1(name, t)
 
@@ -205,7 +199,7 @@ def forward_train(model, image: torch.Tensor, intrinsics: torch.Tensor, dt=torch
     def stem7x7(name, fr):                                       # 7x7, pad 3 conv on the RGB frames as im2col rows + the MFMA GEMM
         w = P[name + ".weight"]                                  # [Cout, 3, 7, 7]
         n_, _, h_, w_ = fr.shape
-        if fr.requires_grad or fr.dtype != torch.float32 or not _IM2COL:      # a gradient for the image: torch differentiates unfold / pad
+        if fr.requires_grad or fr.dtype != torch.float32:      # a gradient for the image: torch differentiates unfold / pad
             f = lambda u: F.unfold(u.to(adt), 7, padding=3).transpose(1, 2)          # [n, h*w, 147] in (c, ky, kx) order = weight.flatten(1)
             cols = chunked(f, fr, h_ * w_ * 147)
             cols = F.pad(cols, (0, 256 - 147))     # 256 columns: whole tiles for the reduction-major weight-gradient kernel (no transposes)

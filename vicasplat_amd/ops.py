@@ -5,7 +5,6 @@ Every function requires HIP device tensors and raises otherwise -- there is no P
 """
 from __future__ import annotations
 
-import os
 from typing import Optional
 
 import torch
@@ -1198,9 +1197,6 @@ def gemm_wgrad_split_atn(a: torch.Tensor, w: SplitWeight, out: torch.Tensor, ksp
     return out
 
 
-_WGRAD_ATN = os.environ.get("VS_WGRAD_ATN", "1") != "0"       # 0: the round-3 route (both operands through transposing passes): same-box A/B
-
-
 def _wgrad_split(dyT: torch.Tensor, xT: SplitWeight, out: torch.Tensor) -> torch.Tensor:
     M, N, K = dyT.shape[0], xT.shape[0], dyT.shape[1]
     if M % 256 == 0 and N % 256 == 0:
@@ -1254,7 +1250,7 @@ def linear_backward_split(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, *,
         if need_db:
             db = torch.empty(N, dtype=torch.float32, device=dev)          # the bias gradient rides on the transpose of dY
         dw = torch.empty((N, K), dtype=torch.float32, device=dev)
-        if _WGRAD_ATN and N % 256 == 0 and K % 256 == 0:
+        if N % 256 == 0 and K % 256 == 0:
             # dW^T [K, N] = X^T dY with X read as it is (reduction-major A operand); only dY goes through a transposing (packing) pass
             dyTp = transpose_pack_split(dys, Mp, colsum=db)               # [N, Mp] packed
             tiles = (N // 256) * (K // 256)
@@ -1342,9 +1338,6 @@ def attention_backward_split(qkv_q: torch.Tensor, qkv_k: torch.Tensor, qkv_v: to
     return dq, dk, dv
 
 
-_WGRAD_STREAM = os.environ.get("VS_WGRAD_STREAM", "1") != "0"
-
-
 def conv3x3_wgrad_split_stream(dy: torch.Tensor, x: torch.Tensor, *, relu_in: bool = False):
     """dw9 [9, Cin, Cout] (tap = ky * 3 + kx) and db [Cout] of a 3x3 convolution (stride 1, pad 1) from x [N,H,W,Cin] and dy [N,H,W,Cout] f32 NHWC,
     split class, one streaming pass (vs_conv3x3_wgrad_split_stream); Cin, Cout multiples of 64, W a multiple of 32."""
@@ -1390,7 +1383,7 @@ def conv3x3_backward_split(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, *
     # shifts are column offsets of this operand: LDS-DMA reads any 4-byte aligned f32 address), W = dY^T [Cout, pixels] packed (hi, lo);
     # out[tap] = [Cin, Cout].  Two transposing passes instead of nine packed shifted images.
     P = N * H * W
-    if _WGRAD_ATN and Cin % 256 == 0 and Cout % 256 == 0:
+    if Cin % 256 == 0 and Cout % 256 == 0:
         # X read as it is by the reduction-major A operand (tap shift = pixel-row shift, zero page outside the image): only dY goes through a
         # transposing (packing) pass, which also yields the bias gradient
         tiles = (Cin // 256) * (Cout // 256) * 9
@@ -1404,7 +1397,7 @@ def conv3x3_backward_split(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, *
                                                     int(relu_in), ks, L.ptr(ws), ws.numel() * 4, 0, L.stream_ptr(dev))
         L.check(rc, "vs_conv3x3_wgrad_split_atn")
         return dx, dw9.view(3, 3, Cin, Cout).permute(3, 2, 0, 1).contiguous(), db
-    if _WGRAD_STREAM and Cin % 64 == 0 and Cout % 64 == 0 and W % 32 == 0:
+    if Cin % 64 == 0 and Cout % 64 == 0 and W % 32 == 0:
         # narrow layers (the pts3d head's 256 -> 128 and 128 -> 128 convolutions): one streaming pass over X and dY as they are
         # (csrc/conv_wgrad_stream.hip) instead of two transposing passes + nine 128 x 128 tiles per K slice on the 4-wave kernel
         dw9, db = conv3x3_wgrad_split_stream(dy, x, relu_in=relu_in)
