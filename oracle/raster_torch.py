@@ -123,6 +123,10 @@ def rasterize(means, cov33, shs, opac, c2w, K, near, far, H, W, bg, tau=None, sh
     dirs = dirs / dirs.norm(dim=1, keepdim=True)
     rgb = torch.clamp(eval_sh(sh_degree, shs, dirs), min=0.0)
 
+    # the render loop reads exactly these tensors, so autograd w.r.t. them gives the render backward's records (screen-space mean in
+    # pixels, conic (A, B, C), colour, depth, opacity); zr is vz's value as a node of its own (vz also feeds the projection)
+    conic = torch.stack([A, B, Cc], -1)
+    zr = vz.clone()
     order = sorted(range(P), key=lambda i: (float(vz[i]), i))
     ys, xs = torch.meshgrid(torch.arange(H, dtype=dt), torch.arange(W, dtype=dt), indexing="ij")
     tyi, txi = torch.div(ys, 16, rounding_mode="floor"), torch.div(xs, 16, rounding_mode="floor")
@@ -136,7 +140,7 @@ def rasterize(means, cov33, shs, opac, c2w, K, near, far, H, W, bg, tau=None, sh
             continue
         intile = (txi >= rminx[i]) & (txi < rmaxx[i]) & (tyi >= rminy[i]) & (tyi < rmaxy[i])
         dx, dy = pix[i, 0] - xs, pix[i, 1] - ys
-        power = -0.5 * (A[i] * dx * dx + Cc[i] * dy * dy) - B[i] * dx * dy
+        power = -0.5 * (conic[i, 0] * dx * dx + conic[i, 2] * dy * dy) - conic[i, 1] * dx * dy
         G = torch.exp(power)
         raw = opac[i] * G
         alpha = raw + (torch.clamp(raw, max=0.99) - raw).detach()  # straight-through, as upstream's backward
@@ -147,12 +151,12 @@ def rasterize(means, cov33, shs, opac, c2w, K, near, far, H, W, bg, tau=None, sh
         ok = ok & (~stop)
         w = torch.where(ok, alpha * T, torch.zeros_like(T))
         Cimg = Cimg + rgb[i][:, None, None] * w
-        Dimg = Dimg + vz[i] * w
+        Dimg = Dimg + zr[i] * w
         n_touched[i] = int((ok & (test_T > 0.5)).sum())
         T = torch.where(ok, test_T, T)
     color = Cimg + T * torch.as_tensor(bg, dtype=dt)[:, None, None]
     if return_aux:
         return color, Dimg, 1 - T, dict(radius=radius, visible=visible, n_touched=n_touched, pix=pix, rgb=rgb,
-                                        conic=torch.stack([A, B, Cc], -1), depth=vz,
+                                        conic=conic, depth=vz, render_inputs=(pix, conic, rgb, zr, opac),
                                         rect=torch.stack([rminx, rminy, rmaxx, rmaxy], -1))
     return color, Dimg, 1 - T

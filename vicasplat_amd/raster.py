@@ -116,9 +116,13 @@ def _forward_impl(means3D, cov3D, shs, colors_precomp, opacities, viewmatrix, pr
 
 
 def forward_debug(means3D, cov3D, opacities, viewmatrix, projmatrix, campos, tanfov, background, H, W, *, shs=None,
-                  colors_precomp=None, sh_degree=0, sh_rgb_major=False, cam_scene=None, count_touched=True) -> dict:
-    """Forward + typed views of the internal buffers (for the parity tests: integer data must be bit-exact)."""
+                  colors_precomp=None, sh_degree=0, sh_rgb_major=False, cam_scene=None, count_touched=True,
+                  save_for_backward=False) -> dict:
+    """Forward + typed views of the internal buffers (for the parity tests: integer data must be bit-exact).  save_for_backward: also
+    store the blending checkpoints, as a differentiated call does (backward_debug then takes the segment-replay route)."""
     flags = (L.VS_RASTER_SH_RGB_MAJOR if sh_rgb_major else 0) | (L.VS_RASTER_COUNT_TOUCHED if count_touched else 0)
+    if save_for_backward:
+        flags |= L.VS_RASTER_SAVE_FOR_BACKWARD
     Cn = viewmatrix.shape[0]
     if cam_scene is not None:
         cam_scene = cam_scene.to(torch.int32).contiguous()
@@ -137,6 +141,32 @@ def forward_debug(means3D, cov3D, opacities, viewmatrix, projmatrix, campos, tan
                 point_list=t[L.VS_BUF_POINT_LIST].view(torch.int32)[:R],
                 final_T=t[L.VS_BUF_FINAL_T].view(torch.float32)[:Cn * H * W].view(Cn, H, W),
                 n_contrib=t[L.VS_BUF_N_CONTRIB].view(torch.int32)[:Cn * H * W].view(Cn, H, W), _state=st)
+
+
+def backward_debug(fwd: dict, dL_dcolor, dL_ddepth=None) -> dict:
+    """vs_raster_backward on the state of a forward_debug call, with EVERY output of VsRasterGrads requested (dL_dmeans2D per camera,
+    dL_dcolors_precomp / dL_dshs per scene, dL_dtau): the route is the forward's (checkpoints saved or not)."""
+    st = fwd["_state"]
+    S, P, Cn, M, H, W, cov33 = st["dims"]
+    inp, out = st["inp"], st["out"]
+    dev = fwd["color"].device
+    g_color = _f32c(dL_dcolor)
+    g_depth = _f32c(dL_ddepth)
+    r = dict(means3D=torch.empty((S, P, 3), dtype=torch.float32, device=dev),
+             cov3D=torch.empty((S, P, 3, 3) if cov33 else (S, P, 6), dtype=torch.float32, device=dev),
+             shs=torch.empty((S, P, M, 3), dtype=torch.float32, device=dev) if inp.shs else None,
+             colors_precomp=torch.empty((S, P, 3), dtype=torch.float32, device=dev) if inp.colors_precomp else None,
+             opacities=torch.empty((S, P), dtype=torch.float32, device=dev),
+             means2D=torch.empty((Cn, P, 2), dtype=torch.float32, device=dev),
+             tau=torch.empty((Cn, 6), dtype=torch.float32, device=dev))
+    g = L.VsRasterGrads()
+    g.dL_dcolor, g.dL_ddepth = L.ptr(g_color), L.ptr(g_depth)
+    g.dL_dmeans3D, g.dL_dcov3D, g.dL_dshs = L.ptr(r["means3D"]), L.ptr(r["cov3D"]), L.ptr(r["shs"])
+    g.dL_dcolors_precomp, g.dL_dopacities = L.ptr(r["colors_precomp"]), L.ptr(r["opacities"])
+    g.dL_dmeans2D, g.dL_dtau = L.ptr(r["means2D"]), L.ptr(r["tau"])
+    _backward_impl(inp, out, g, dev)
+    torch.cuda.synchronize(dev)
+    return r
 
 
 def _backward_impl(inp, out, grads, dev) -> None:
