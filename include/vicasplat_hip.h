@@ -547,6 +547,36 @@ int vs_probe_mfma_rate(const void *operands, float *scratch, int32_t iters, doub
 int vs_range_check(const void *x, int64_t rows, int32_t cols, int64_t ld, int32_t kind, float limit, int32_t *flags, int32_t slot,
                    vs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * SSIM (ABI 9), csrc/ssim.hip.  x, y: f32 NCHW contiguous [N, C, H, W]; every (image, channel) plane is scored on the VALID window
+ * positions, an (H - ws + 1) x (W - ws + 1) map.  taps: ws host floats (ws odd, 1 <= ws <= 11, H and W >= ws).  Per map pixel, with the
+ * five moments mu_x, mu_y, E[x^2], E[y^2], E[xy] of the separable window:  v_x = cov_norm (E[x^2] - mu_x^2), v_y, v_xy likewise,
+ * S = (2 mu_x mu_y + c1)(2 v_xy + c2) / ((mu_x^2 + mu_y^2 + c1)(v_x + v_y + c2)).
+ *   - the evaluation metric, compute_ssim (src/evaluation/metrics.py:46-62, called from src/model/model_wrapper.py:359-364, :611-612 and
+ *     src/evaluation/metric_computer.py:66): skimage structural_similarity(win_size=11, gaussian_weights=True, data_range=1): taps of
+ *     gaussian_filter(sigma 1.5, truncate 3.5), cov_norm = 121 / 120, c1 = 0.01^2, c2 = 0.03^2.  Its reflect padding + 5-pixel crop
+ *     is exactly this valid map: no surviving map pixel reads a reflected sample.
+ *   - the SSIM loss (src/loss/loss_ssim.py:129-190, used by src/evaluation/pose_evaluator.py:136-141): taps of _fspecial_gauss_1d (or the
+ *     caller's window), cov_norm = 1; VS_SSIM_COMPONENTS adds the brightness, contrast and structure maps of _ssim (:105-124: variances clamped
+ *     at eps^2, sigma_xy = sign * min(sqrt(v_x v_y), |v_xy|), c3 = c2 / 2, contrast and structure clamped at 0.98).
+ * flags: VS_SSIM_COMPONENTS (forward: also the component maps); VS_SSIM_UNIT_WINDOW (the window's total weight is taken as exactly 1,
+ * as for the metric's float64 taps; without it the weight is the square of the taps' sum, as for the loss's float32 window).
+ * vs_ssim_forward writes the map means: out_plane [nq][N * C] (per plane) and out_image [nq][N] (per image: the mean over channels), nq = 1
+ * (S) or 4 (S, brightness, contrast, structure) with VS_SSIM_COMPONENTS; either output may be null, not both.  workspace: device memory of
+ * vs_ssim_workspace_bytes(...) bytes (one partial sum per workgroup; reduced in a fixed order in f64: bit-identical from run to run).
+ * vs_ssim_backward: the gradient of sum_p g_ssim[p] * mean(S_p) + g_structure[p] * mean(structure_p) with respect to x and y
+ * (torch autograd's conventions for the clamps, sign and minimum of the loss); g_ssim / g_structure: device f32 [N * C], null = zeros;
+ * dx / dy: device f32 [N, C, H, W] (overwritten), either may be null, not both.  Asynchronous on `stream`; no atomics.
+ * ------------------------------------------------------------------------------------------------ */
+enum { VS_SSIM_COMPONENTS = 1, VS_SSIM_UNIT_WINDOW = 2 };
+int64_t vs_ssim_workspace_bytes(int32_t N, int32_t C, int32_t H, int32_t W, int32_t win_size, int32_t flags);
+int vs_ssim_forward(const float *x, const float *y, int32_t N, int32_t C, int32_t H, int32_t W, const float *taps, int32_t win_size,
+                    float cov_norm, float c1, float c2, int32_t flags, float *workspace, float *out_plane, float *out_image,
+                    vs_stream_t stream);
+int vs_ssim_backward(const float *x, const float *y, int32_t N, int32_t C, int32_t H, int32_t W, const float *taps, int32_t win_size,
+                     float cov_norm, float c1, float c2, int32_t flags, const float *g_ssim, const float *g_structure, float *dx, float *dy,
+                     vs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

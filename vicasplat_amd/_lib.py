@@ -15,7 +15,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.environ.get("VICASPLAT_HIP_LIB") or os.path.join(_HERE, "libvicasplat_hip.so")   # (override: A/B runs of two builds)
 _lock = threading.Lock()
-ABI_VERSION = 8     # == vs_abi_version() of csrc/api.hip; INTEGRATION.md lists the entries of every version
+ABI_VERSION = 9     # == vs_abi_version() of csrc/api.hip; INTEGRATION.md lists the entries of every version
 _lib = None
 
 VS_BUF_GEOM, VS_BUF_RECT, VS_BUF_CLAMPED, VS_BUF_TILE_RANGES, VS_BUF_TILE_CURSOR, VS_BUF_KEYS, VS_BUF_POINT_LIST, \
@@ -24,6 +24,8 @@ VS_RASTER_COUNT_TOUCHED = 1
 VS_RASTER_SAVE_FOR_BACKWARD = 2
 VS_RASTER_SH_RGB_MAJOR = 4
 VS_RASTER_COV_3X3 = 8
+VS_SSIM_COMPONENTS = 1
+VS_SSIM_UNIT_WINDOW = 2
 
 AllocFn = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_int32, C.c_size_t)
 
@@ -204,6 +206,12 @@ def lib() -> C.CDLL:
                            ("vs_im2col7x7_rgb", [vp, vp, i32, i32, i32, i32, i32, vp])):
                 getattr(L, nm).restype = C.c_int
                 getattr(L, nm).argtypes = at
+            L.vs_ssim_workspace_bytes.restype = i64
+            L.vs_ssim_workspace_bytes.argtypes = [i32] * 6
+            L.vs_ssim_forward.restype = C.c_int
+            L.vs_ssim_forward.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, f32, f32, f32, i32, vp, vp, vp, vp]
+            L.vs_ssim_backward.restype = C.c_int
+            L.vs_ssim_backward.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, f32, f32, f32, i32, vp, vp, vp, vp, vp]
             if hasattr(L, "vs_raster_backward"):
                 L.vs_raster_backward.restype = C.c_int
                 L.vs_raster_backward.argtypes = [C.POINTER(VsRasterIn), C.POINTER(VsRasterOut), C.POINTER(VsRasterGrads),

@@ -782,3 +782,34 @@ class GaussianAdapterFn(torch.autograd.Function):
 
 def gaussian_adapter(pts, gs, sh_mask, *, scale_act="softplus", scale_min=0.0, scale_max=0.0, opacity_exponent=1.0):
     return GaussianAdapterFn.apply(pts, gs, sh_mask, scale_act, scale_min, scale_max, opacity_exponent)
+
+
+class SsimFn(torch.autograd.Function):
+    """Per-plane means (ssim, brightness, contrast, structure) [N, C] of src/loss/loss_ssim.py `_ssim` (:58-126) on the HIP kernels
+    (ops.ssim_forward / ops.ssim_backward).  The ssim and structure means are differentiable in X and Y; brightness and contrast are not
+    (nothing on the reference's paths back-propagates through them).  Without `components` the last three are zeros."""
+
+    @staticmethod
+    def forward(ctx, X, Y, taps, c1, c2, components):
+        per_plane, _ = ops.ssim_forward(X, Y, taps, 1.0, c1, c2, components)
+        ctx.save_for_backward(X, Y)
+        ctx.meta = (taps, c1, c2, components)
+        if components:
+            s, b, c, t = per_plane.unbind(0)
+        else:
+            s = per_plane[0]
+            b, c, t = torch.zeros_like(s), torch.zeros_like(s), torch.zeros_like(s)
+        ctx.mark_non_differentiable(b, c)
+        ctx.set_materialize_grads(False)
+        return s, b, c, t
+
+    @staticmethod
+    def backward(ctx, gs, _gb, _gc, gt):
+        X, Y = ctx.saved_tensors
+        taps, c1, c2, components = ctx.meta
+        if not components:
+            gt = None
+        if gs is None and gt is None:
+            return None, None, None, None, None, None
+        dx, dy = ops.ssim_backward(X, Y, taps, 1.0, c1, c2, gs, gt, need_dx=ctx.needs_input_grad[0], need_dy=ctx.needs_input_grad[1])
+        return (None if dx is None else dx.to(X.dtype)), (None if dy is None else dy.to(Y.dtype)), None, None, None, None

@@ -4,6 +4,8 @@ What is here runs on the HIP rasterizer through `DecoderSplattingCUDA` and is wh
 scripts do around the encoder/decoder:
   * `mse_loss`                — LossMse.forward, src/loss/loss_mse.py:23-31
   * `compute_psnr`            — src/evaluation/metrics.py:21-29
+  * `compute_ssim`            — src/evaluation/metrics.py:46-62 (skimage structural_similarity, per image) on the HIP SSIM kernels
+  * `ssim`                    — src/loss/loss_ssim.py:129-190 (the differentiable SSIM of pose_evaluator.py:136-141; `_ssim` :58-126)
   * `se3_exp`, `update_pose`  — src/misc/cam_utils.py:59-142 (batched, no per-camera Python loop)
   * `align_poses`             — ModelWrapper.test_step_align, src/model/model_wrapper.py:442-513
   * `export_ply`              — src/model/ply_export.py:31-90 (own binary writer, no plyfile dependency)
@@ -41,6 +43,69 @@ def compute_psnr(ground_truth: Tensor, predicted: Tensor) -> Tensor:
     return -10 * ((gt - pr) ** 2).flatten(1).mean(1).log10()
 
 
+def _gaussian_taps_f64(sigma: float, radius: int) -> list[float]:
+    """Taps of scipy.ndimage.gaussian_filter (what skimage's gaussian_weights uses): exp(-x^2 / (2 sigma^2)), x = -radius..radius, sum 1."""
+    x = np.arange(-radius, radius + 1, dtype=np.float64)
+    g = np.exp(-0.5 / (sigma * sigma) * x * x)
+    return (g / g.sum()).tolist()
+
+
+_SSIM_METRIC_TAPS = _gaussian_taps_f64(1.5, int(3.5 * 1.5 + 0.5))     # sigma 1.5, truncate 3.5: radius 5, 11 taps
+
+
+@torch.no_grad()
+def compute_ssim(ground_truth: Tensor, predicted: Tensor) -> Tensor:
+    """SSIM per image of [batch, channel, h, w] tensors: skimage structural_similarity(gt, hat, win_size=11, gaussian_weights=True,
+    channel_axis=0, data_range=1.0), as metrics.py:46-62 applies it, without the host round trip: one HIP forward over every plane
+    (vs_ssim_forward; sample covariances, cov_norm = 121 / 120; the map mean over the 5-pixel-cropped interior, averaged over channels).
+    No clipping of the inputs.  Returns a device tensor [batch] of predicted.dtype; no host synchronisation."""
+    from . import ops
+    if ground_truth.shape != predicted.shape or predicted.dim() != 4:
+        raise ValueError(f"compute_ssim takes two [batch, channel, h, w] tensors of one shape, got {tuple(ground_truth.shape)} "
+                         f"and {tuple(predicted.shape)}")
+    if min(predicted.shape[-2:]) < 11:
+        raise ValueError(f"win_size exceeds image extent: an image of {tuple(predicted.shape[-2:])} is smaller than the 11 x 11 window")
+    _, per_image = ops.ssim_forward(ground_truth, predicted, _SSIM_METRIC_TAPS, 121.0 / 120.0, 0.01 ** 2, 0.03 ** 2,
+                                     unit_window=True)
+    return per_image[0].to(predicted.dtype)
+
+
+def _fspecial_gauss_1d(size: int, sigma: float) -> Tensor:
+    """The loss window of loss_ssim.py:12-26, in float32 on the host (the same float32 operations, so the same taps)."""
+    coords = torch.arange(size, dtype=torch.float) - size // 2
+    g = torch.exp(-(coords ** 2) / (2 * sigma ** 2))
+    return g / g.sum()
+
+
+def ssim(X: Tensor, Y: Tensor, data_range: float = 255, size_average: bool = True, win_size: int = 11, win_sigma: float = 1.5,
+         win: Tensor | None = None, K=(0.01, 0.03), nonnegative_ssim: bool = False, retrun_seprate: bool = False):
+    """The SSIM loss of loss_ssim.py:129-190 (keyword names included) on the HIP kernels: valid convolution with the 1-D Gaussian window,
+    no covariance correction.  Returns (ssim, brightness, contrast, structure): scalars with size_average, else per-image [N] means over
+    channels; the last three are zeros unless retrun_seprate.  Differentiable in X and Y through ssim and structure (autograd.SsimFn);
+    brightness and contrast are not.  A caller-supplied `win` is one 1-D window (its first row if it holds one per channel).  [N, C, H, W]
+    inputs only, H and W >= win_size."""
+    from . import autograd as A
+    if X.shape != Y.shape:
+        raise ValueError(f"Input images should have the same dimensions, but got {X.shape} and {Y.shape}.")
+    for d in range(X.dim() - 1, 1, -1):
+        X, Y = X.squeeze(dim=d), Y.squeeze(dim=d)
+    if X.dim() != 4:
+        raise ValueError(f"Input images should be 4-d tensors [N, C, H, W] (5-d inputs are not supported), but got {X.shape}")
+    if win is not None:
+        win_size = win.shape[-1]
+    if win_size % 2 != 1:
+        raise ValueError("Window size should be odd.")
+    if min(X.shape[-2:]) < win_size:
+        raise ValueError(f"SSIM needs images of at least {win_size} x {win_size}, got {tuple(X.shape[-2:])}")
+    taps = (_fspecial_gauss_1d(win_size, win_sigma) if win is None else win.detach().reshape(-1, win_size)[0].float().cpu()).tolist()
+    K1, K2 = K
+    s, b, c, t = A.SsimFn.apply(X, Y, tuple(taps), (K1 * data_range) ** 2, (K2 * data_range) ** 2, bool(retrun_seprate))
+    if nonnegative_ssim:
+        s = torch.relu(s)
+    out = (s, b, c, t) if not X.is_floating_point() else tuple(v.to(X.dtype) for v in (s, b, c, t))
+    return tuple(v.mean() for v in out) if size_average else tuple(v.mean(1) for v in out)
+
+
 def _skew(w: Tensor) -> Tensor:
     z = torch.zeros_like(w[..., 0])
     return torch.stack([z, -w[..., 2], w[..., 1], w[..., 2], z, -w[..., 0], -w[..., 1], w[..., 0], z], -1).unflatten(-1, (3, 3))
@@ -72,10 +137,12 @@ def update_pose(cam_trans_delta: Tensor, cam_rot_delta: Tensor, extrinsics: Tens
 
 def align_poses(decoder, gaussians, target_image: Tensor, extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor,
                 steps: int = 100, rot_lr: float = 0.005, trans_lr: float = 0.005, mse_weight: float = 1.0,
-                return_history: bool = False):
+                return_history: bool = False, ssim_structure_weight: float = 0.0):
     """Test-time pose alignment: Adam on per-camera twist deltas through the rasterizer's camera-Jacobian backward,
     folding the delta into the extrinsics after every step (model_wrapper.py:442-513).
-    target_image [b,v,3,h,w]; extrinsics [b,v,4,4] c2w. Returns the refined extrinsics (and the loss history)."""
+    target_image [b,v,3,h,w]; extrinsics [b,v,4,4] c2w. Returns the refined extrinsics (and the loss history).
+    ssim_structure_weight w != 0 adds w * (1 - structure) of ssim(target, render, data_range=1.0, retrun_seprate=True) to every step's
+    loss, the structure term of pose_evaluator.py:136-141 (off by default, as that loop ships with number_steps = 0)."""
     b, v, _, h, w = target_image.shape
     dev = target_image.device
     gaussians = Gaussians(gaussians.means.detach(), gaussians.covariances.detach(), gaussians.harmonics.detach(),
@@ -105,6 +172,10 @@ def align_poses(decoder, gaussians, target_image: Tensor, extrinsics: Tensor, in
                     else:
                         flags.append(scope.overflow_flag())
                 loss = mse_loss(out.color, target_image, mse_weight)
+                if ssim_structure_weight != 0.0:
+                    structure = ssim(target_image.flatten(0, 1), out.color.flatten(0, 1), size_average=True, data_range=1.0,
+                                     retrun_seprate=True, win_size=11)[3]
+                    loss = loss + ssim_structure_weight * (1 - structure)
                 loss.backward()
                 history.append(loss.detach())
                 with torch.no_grad():

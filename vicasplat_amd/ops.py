@@ -1442,3 +1442,55 @@ def sustained_mfma_tflops(device, ms_target: float = 40.0) -> float:
     iters = max(20000, int(20000 * ms_target / max(ms, 1e-3)))
     ms, f = run(iters)
     return f / (ms * 1e-3) / 1e12
+
+
+def _ssim_args(x: torch.Tensor, y: torch.Tensor, taps):
+    """(x, y, host taps) of the SSIM kernels: f32 NCHW contiguous device tensors of one shape, taps a ctypes float array."""
+    import ctypes
+    if x.shape != y.shape or x.dim() != 4:
+        raise ValueError(f"SSIM kernels take two [N, C, H, W] tensors of one shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    dev = L.require_device(x, y)
+    taps = [float(t) for t in taps]
+    return dev, x.contiguous().float(), y.contiguous().float(), (ctypes.c_float * len(taps))(*taps), len(taps)
+
+
+def ssim_forward(x: torch.Tensor, y: torch.Tensor, taps, cov_norm: float, c1: float, c2: float, components: bool = False,
+                 unit_window: bool = False):
+    """Per-plane and per-image means of the SSIM map (and, with `components`, of the brightness, contrast and structure maps) of x against
+    y on the valid window positions (vs_ssim_forward).  unit_window: the taps stand for a window of total weight exactly 1 (float64 taps
+    rounded to float32); otherwise their own sum counts.  Returns (per_plane [nq, N, C], per_image [nq, N]), f32, nq = 4 if components else 1.
+    Asynchronous on the current stream: no host synchronisation."""
+    dev, x, y, tp, ws = _ssim_args(x, y, taps)
+    N, C, H, W = x.shape
+    flags = (L.VS_SSIM_COMPONENTS if components else 0) | (L.VS_SSIM_UNIT_WINDOW if unit_window else 0)
+    nbytes = L.lib().vs_ssim_workspace_bytes(N, C, H, W, ws, flags)
+    L.check(nbytes, "vs_ssim_workspace_bytes")
+    nq = 4 if components else 1
+    work = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    per_plane = torch.empty((nq, N, C), dtype=torch.float32, device=dev)
+    per_image = torch.empty((nq, N), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.lib().vs_ssim_forward(L.ptr(x), L.ptr(y), N, C, H, W, tp, ws, cov_norm, c1, c2, flags, L.ptr(work),
+                                     L.ptr(per_plane), L.ptr(per_image), L.stream_ptr(dev))
+    L.check(rc, "vs_ssim_forward")
+    return per_plane, per_image
+
+
+def ssim_backward(x: torch.Tensor, y: torch.Tensor, taps, cov_norm: float, c1: float, c2: float, g_ssim: Optional[torch.Tensor],
+                  g_structure: Optional[torch.Tensor], need_dx: bool = True, need_dy: bool = True, unit_window: bool = False):
+    """(dx, dy) of sum g_ssim[n, c] * ssim[n, c] + g_structure[n, c] * structure[n, c], the per-plane means of ssim_forward
+    (vs_ssim_backward).  g_*: [N, C] or None (zeros); an output not asked for is None."""
+    dev, x, y, tp, ws = _ssim_args(x, y, taps)
+    N, C, H, W = x.shape
+    gs = None if g_ssim is None else g_ssim.detach().reshape(N * C).contiguous().float()
+    gt = None if g_structure is None else g_structure.detach().reshape(N * C).contiguous().float()
+    dx = torch.empty_like(x) if need_dx else None
+    dy = torch.empty_like(y) if need_dy else None
+    if dx is None and dy is None:
+        return None, None
+    with torch.cuda.device(dev):
+        rc = L.lib().vs_ssim_backward(L.ptr(x), L.ptr(y), N, C, H, W, tp, ws, cov_norm, c1, c2,
+                                      L.VS_SSIM_UNIT_WINDOW if unit_window else 0, L.ptr(gs), L.ptr(gt), L.ptr(dx),
+                                      L.ptr(dy), L.stream_ptr(dev))
+    L.check(rc, "vs_ssim_backward")
+    return dx, dy
