@@ -577,6 +577,40 @@ int vs_ssim_backward(const float *x, const float *y, int32_t N, int32_t C, int32
                      float cov_norm, float c1, float c2, int32_t flags, const float *g_ssim, const float *g_structure, float *dx, float *dy,
                      vs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * LPIPS-VGG (ABI 10), csrc/lpips.hip: the glue of lpips.LPIPS(net="vgg", version="0.1") in eval mode (src/loss/loss_lpips.py:27-54, the
+ * training term; src/evaluation/metrics.py:37-44, the metric) around its 13 convolutions, which run on vs_conv3x3_split_nhwc (and, for the
+ * data gradient, on the same entry with the flipped, channel-transposed weights and relu_out = 2).  H and W multiples of 16; activations f32
+ * NHWC contiguous, 16-byte aligned; the taps s = 1..5 are relu1_2 / 2_2 / 3_3 / 4_3 / 5_3 at (H >> (s-1)) x (W >> (s-1)) with 64 / 128 /
+ * 256 / 512 / 512 channels.  Every entry is asynchronous on `stream` and uses no atomics (bit-identical from run to run).
+ *   vs_lpips_prep: img f32 NCHW [N,3,H,W] -> out [N,H,W,32]: x <- 2x - 1 if `normalize` (lpips.py LPIPS.forward), then the ScalingLayer
+ *     (x - shift) / scale with shift (-0.030, -0.088, -0.188), scale (0.458, 0.448, 0.450); channels 3..31 zero (conv1_1's Cin padded to 32).
+ *   vs_lpips_prep_backward: g32 [N,H,W,32] (conv1_1's data gradient) -> dimg [N,3,H,W] = g32[..., c] / scale_c (x 2 if `normalize`),
+ *     unscaled by 2^(e_n - scale_log2) where g[n] = m 2^e_n (frexp; g the [N] upstream gradient given to vs_lpips_head_backward).
+ *   vs_lpips_maxpool: x [N,H,W,C] -> y [N,H/2,W/2,C], 2 x 2 stride 2 (torch max_pool2d(x, 2, 2), the pool before slices 2..5).  H, W even,
+ *     C % 4 == 0.
+ *   vs_lpips_maxpool_backward: dx [N,H,W,C] = (x > 0) * (g_add + dy routed to the FIRST maximum of each window in row-major order, as torch
+ *     breaks ties); x is the pool's input (the tap's post-ReLU activation), dy [N,H/2,W/2,C], g_add (nullable) the tap's head gradient.
+ *   vs_lpips_head_forward: f0, f1, lin: HOST arrays of 5 device pointers (the two images' taps; lin[s] = lin{s}.model.1.weight, C floats).
+ *     out [N] = sum_s mean_pixels sum_c lin_c (f0_c / (|f0| + 1e-10) - f1_c / (|f1| + 1e-10))^2 (lpips.py LPIPS.forward, normalize_tensor).
+ *     workspace: vs_lpips_workspace_bytes(N, H, W) bytes of device memory (one partial per workgroup, reduced in a fixed order in f64).
+ *   vs_lpips_head_backward: d0 / d1: host arrays of 5 device pointers or null (either, not both): the gradient of sum_n g[n] out[n] with
+ *     respect to f0 / f1 at every tap, multiplied by 2^scale_log2 / m_n (g[n] = m_n 2^e_n; the power-of-two scale keeps the split class's
+ *     f16 halves of the data gradients normal) and by the tap's ReLU mask f > 0.  At a pixel whose channel vector is all zero the
+ *     normalisation's derivative is taken as I / (r + eps) (torch autograd gives NaN there).
+ * ------------------------------------------------------------------------------------------------ */
+int64_t vs_lpips_workspace_bytes(int32_t N, int32_t H, int32_t W);
+int vs_lpips_prep(const float *img, int32_t N, int32_t H, int32_t W, int32_t normalize, float *out, vs_stream_t stream);
+int vs_lpips_prep_backward(const float *g32, const float *g, int32_t N, int32_t H, int32_t W, int32_t normalize, int32_t scale_log2, float *dimg,
+                           vs_stream_t stream);
+int vs_lpips_maxpool(const float *x, int32_t N, int32_t H, int32_t W, int32_t C, float *y, vs_stream_t stream);
+int vs_lpips_maxpool_backward(const float *dy, const float *x, const float *g_add, int32_t N, int32_t H, int32_t W, int32_t C, float *dx,
+                              vs_stream_t stream);
+int vs_lpips_head_forward(const float *const *f0, const float *const *f1, const float *const *lin, int32_t N, int32_t H, int32_t W,
+                          float *workspace, float *out, vs_stream_t stream);
+int vs_lpips_head_backward(const float *const *f0, const float *const *f1, const float *const *lin, const float *g, int32_t N, int32_t H,
+                           int32_t W, int32_t scale_log2, float *const *d0, float *const *d1, vs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--scenes", type=int, default=1); ap.add_argument("--views", type=int, default=8); ap.add_argument("--targets", type=int, default=12)   # re10k_8view.yaml:20
 ap.add_argument("--steps", type=int, default=3); ap.add_argument("--warmup", type=int, default=1); ap.add_argument("--checkpoint", action="store_true")
 ap.add_argument("--dtype", default="f16", choices=["f16", "bf16", "split"])
+ap.add_argument("--lpips", action="store_true", help="also time the step with the reference's LPIPS term (LossLpips(backend='hip'), seeded "
+                "He-scaled VGG weights): a second JSON line")
 a = ap.parse_args()
 CDT = {"f16": torch.float16, "bf16": torch.bfloat16, "split": "split"}[a.dtype]
 d = torch.device("cuda:0")
@@ -47,3 +49,22 @@ print(json.dumps(dict(config="re10k_8view training step fwd+bwd+AdamW", dtype=a.
                       device_mallocs_in_timed_steps=torch.cuda.memory_stats()["num_device_alloc"] - st0["num_device_alloc"],
                       device_frees_in_timed_steps=torch.cuda.memory_stats()["num_device_free"] - st0["num_device_free"],
                       alloc_retries=torch.cuda.memory_stats()["num_alloc_retries"])))
+if a.lpips:     # the reference objective's LPIPS term (config/loss/lpips.yaml: weight 0.05 from step 0) on the HIP kernels
+    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "tests"))
+    import lpips_f64
+    loss_lpips = callers.LossLpips(lpips_f64.fake_state_dict(0), weight=0.05, apply_after_step=0, backend="hip", device=d)
+
+    def lpips(render, batch, out):
+        return loss_lpips(render.color, batch["target"]["image"], 0)
+
+    for _ in range(a.warmup):
+        r = callers.training_step(enc, dec, batch, opt, compute_dtype=CDT, extra_losses=[lpips])
+    torch.cuda.reset_peak_memory_stats()
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    for _ in range(a.steps):
+        r = callers.training_step(enc, dec, batch, opt, compute_dtype=CDT, extra_losses=[lpips])
+    torch.cuda.synchronize(); dt2 = (time.perf_counter() - t0) / a.steps
+    print(json.dumps(dict(config="re10k_8view training step fwd+bwd+AdamW, mse + lpips (hip)", dtype=a.dtype, scenes=B, views=V, targets=Vt,
+                          ms_per_step=round(dt2 * 1e3, 1), ms_per_step_without_lpips=round(dt * 1e3, 1), lpips_ms=round((dt2 - dt) * 1e3, 1),
+                          loss=float(r["loss"]), loss_lpips=float(r["loss_lpips"]), skipped=bool(r["skipped"]),
+                          peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2**30, 1))))

@@ -15,7 +15,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.environ.get("VICASPLAT_HIP_LIB") or os.path.join(_HERE, "libvicasplat_hip.so")   # (override: A/B runs of two builds)
 _lock = threading.Lock()
-ABI_VERSION = 9     # == vs_abi_version() of csrc/api.hip; INTEGRATION.md lists the entries of every version
+ABI_VERSION = 10    # == vs_abi_version() of csrc/api.hip; INTEGRATION.md lists the entries of every version
 _lib = None
 
 VS_BUF_GEOM, VS_BUF_RECT, VS_BUF_CLAMPED, VS_BUF_TILE_RANGES, VS_BUF_TILE_CURSOR, VS_BUF_KEYS, VS_BUF_POINT_LIST, \
@@ -212,6 +212,16 @@ def lib() -> C.CDLL:
             L.vs_ssim_forward.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, f32, f32, f32, i32, vp, vp, vp, vp]
             L.vs_ssim_backward.restype = C.c_int
             L.vs_ssim_backward.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, f32, f32, f32, i32, vp, vp, vp, vp, vp]
+            L.vs_lpips_workspace_bytes.restype = i64
+            L.vs_lpips_workspace_bytes.argtypes = [i32] * 3
+            for nm, at in (("vs_lpips_prep", [vp, i32, i32, i32, i32, vp, vp]),
+                           ("vs_lpips_prep_backward", [vp, vp, i32, i32, i32, i32, i32, vp, vp]),
+                           ("vs_lpips_maxpool", [vp, i32, i32, i32, i32, vp, vp]),
+                           ("vs_lpips_maxpool_backward", [vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+                           ("vs_lpips_head_forward", [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+                           ("vs_lpips_head_backward", [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp])):
+                getattr(L, nm).restype = C.c_int
+                getattr(L, nm).argtypes = at
             if hasattr(L, "vs_raster_backward"):
                 L.vs_raster_backward.restype = C.c_int
                 L.vs_raster_backward.argtypes = [C.POINTER(VsRasterIn), C.POINTER(VsRasterOut), C.POINTER(VsRasterGrads),

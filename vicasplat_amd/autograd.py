@@ -813,3 +813,40 @@ class SsimFn(torch.autograd.Function):
             return None, None, None, None, None, None
         dx, dy = ops.ssim_backward(X, Y, taps, 1.0, c1, c2, gs, gt, need_dx=ctx.needs_input_grad[0], need_dy=ctx.needs_input_grad[1])
         return (None if dx is None else dx.to(X.dtype)), (None if dy is None else dy.to(Y.dtype)), None, None, None, None
+
+
+class LpipsFn(torch.autograd.Function):
+    """lpips.LPIPS(net="vgg", version="0.1").forward(in0, in1, normalize) in eval mode -> [N, 1, 1, 1] on the HIP kernels: the 13 split-class
+    convolutions of `net` (callers.LpipsVgg) and csrc/lpips.hip.  The backward returns a gradient only for the inputs that need one: it
+    keeps the 13 post-ReLU activations of each such side (about 71 MB per 256 x 256 view) and runs the data-gradient chain once per side."""
+
+    @staticmethod
+    def forward(ctx, in0, in1, net, normalize):
+        need0, need1 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        acts0, acts1 = net.features(in0, normalize, keep_all=need0), net.features(in1, normalize, keep_all=need1)
+        taps0, taps1 = net.taps(acts0), net.taps(acts1)
+        d = ops.lpips_head_forward(taps0, taps1, net.lins)
+        ctx.net, ctx.meta = net, (bool(normalize), need0, need1, in0.dtype, in1.dtype)
+        if need0 or need1:
+            keep0 = acts0 if need0 else taps0
+            keep1 = acts1 if need1 else taps1
+            ctx.n0 = len(keep0)
+            ctx.save_for_backward(*keep0, *keep1)
+        ctx.set_materialize_grads(False)
+        return d.view(-1, 1, 1, 1)
+
+    @staticmethod
+    def backward(ctx, gd):
+        normalize, need0, need1, dt0, dt1 = ctx.meta
+        if gd is None or not (need0 or need1):
+            return None, None, None, None
+        net = ctx.net
+        saved = ctx.saved_tensors
+        keep0, keep1 = saved[:ctx.n0], saved[ctx.n0:]
+        taps0 = net.taps(keep0) if need0 else list(keep0)
+        taps1 = net.taps(keep1) if need1 else list(keep1)
+        g = gd.reshape(-1)
+        dt0_, dt1_ = ops.lpips_head_backward(taps0, taps1, net.lins, g, need0, need1)
+        dx0 = net.features_backward(keep0, dt0_, g, normalize).to(dt0) if need0 else None
+        dx1 = net.features_backward(keep1, dt1_, g, normalize).to(dt1) if need1 else None
+        return dx0, dx1, None, None

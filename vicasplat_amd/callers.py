@@ -15,6 +15,7 @@ scripts do around the encoder/decoder:
     src/visualization/camera_trajectory/interpolation.py (the 70-view demo video: cameras share ONE Gaussian set)
   * `camera_loss`, `camera_dq_loss` — src/loss/loss_camera.py:30-80 (dual-quaternion algebra of src/misc/dq.py restated)
   * `LossLpips` — src/loss/loss_lpips.py:27-54 (published LPIPS-VGG algorithm; the pretrained weights must be supplied, see the class)
+  * `LpipsVgg`, `compute_lpips` — lpips.LPIPS(net="vgg") and src/evaluation/metrics.py:37-44 on the HIP kernels (LossLpips(backend="hip"))
   * `configure_optimizer`, `training_step` — ModelWrapper.configure_optimizers / training_step (model_wrapper.py:884-951,
     184-321): AdamW(lr, wd 0.05, betas 0.9/0.95) with the backbone-lr multiplier, encoder -> rasterizer -> MSE ->
     backward on the HIP kernels (vicasplat_amd.autograd) -> optional gradient all-reduce -> clip 0.5 -> step.
@@ -528,8 +529,8 @@ def camera_loss(pred_extrins: Tensor, context_extrinsics: Tensor, weight: float 
 # LPIPS(VGG) -- src/loss/loss_lpips.py:27-54.  The reference instantiates `lpips.LPIPS(net="vgg")` (un-vendored pip package, pretrained
 # VGG-16 + learned linear heads downloaded at construction): neither the package nor its weights exist offline, so the published
 # algorithm is restated here and the WEIGHTS must be supplied -- `torch.save(lpips.LPIPS(net="vgg").state_dict(), path)` on a machine that
-# has them.  Without weights the constructor raises; nothing is silently substituted.  The loss network runs on PyTorch convolutions (it
-# is not part of the encoder / rasterizer hot path and has no counterpart kernel in this library).
+# has them.  Without weights the constructor raises; nothing is silently substituted.  backend="torch" (the default) runs the loss network
+# on PyTorch convolutions; backend="hip" runs the same definition on LpipsVgg (split-class convolutions + csrc/lpips.hip).
 # ---------------------------------------------------------------------------------------------------------------------------
 # STATUS: UNVERIFIED -- no reference weights, package or fixture exists offline, so nothing pins this class against `lpips.LPIPS`; it is
 # NOT part of any parity claim and does NOT count toward SURVEY 8(f)-4.  It is kept as a plug-in point (`extra_losses`).
@@ -537,17 +538,22 @@ class LossLpips(torch.nn.Module):
     """LPIPS with the VGG-16 backbone ("vgg" variant, v0.1): inputs in [0, 1] (`normalize=True` of loss_lpips.py:48-52), scaling layer,
     the five ReLU taps relu1_2 / 2_2 / 3_3 / 4_3 / 5_3, channel-unit-normalised squared differences, non-negative 1x1 linear heads, spatial
     mean, sum over the taps.  forward(prediction [b,v,3,h,w], target [b,v,3,h,w], global_step) -> weight * mean over images; zero before
-    `apply_after_step` (config/loss/lpips.yaml)."""
+    `apply_after_step` (config/loss/lpips.yaml).  backend="hip": the same value and its gradient on the HIP kernels (LpipsVgg, weights
+    packed once on `device`; h and w multiples of 16, inputs on that device)."""
     _SLICES = ((0, 2), (5, 7), (10, 12, 14), (17, 19, 21), (24, 26, 28))   # torchvision vgg16.features conv indices per slice
     _CHANNELS = ((3, 64, 64), (64, 128, 128), (128, 256, 256, 256), (256, 512, 512, 512), (512, 512, 512, 512))
 
-    def __init__(self, weights, weight: float = 0.05, apply_after_step: int = 0):
+    def __init__(self, weights, weight: float = 0.05, apply_after_step: int = 0, backend: str = "torch", device=None):
         super().__init__()
         if weights is None:
             raise RuntimeError("LossLpips needs the state_dict of lpips.LPIPS(net='vgg') (pretrained VGG-16 + linear heads); it is not "
                                "available offline and is never replaced by random weights")
+        if backend not in ("torch", "hip"):
+            raise ValueError(f'LossLpips: backend must be "torch" or "hip", got {backend!r}')
         sd = torch.load(weights, map_location="cpu") if isinstance(weights, (str, Path)) else dict(weights)
-        self.weight, self.apply_after_step = weight, apply_after_step
+        self.weight, self.apply_after_step, self.backend = weight, apply_after_step, backend
+        # backend="hip": the same definition on LpipsVgg (split-class convolutions + csrc/lpips.hip), its weights packed once on `device`
+        self._hip = LpipsVgg(sd, device=device) if backend == "hip" else None
         self.register_buffer("shift", torch.tensor([-0.030, -0.088, -0.188]).view(1, 3, 1, 1), persistent=False)
         self.register_buffer("scale", torch.tensor([0.458, 0.448, 0.450]).view(1, 3, 1, 1), persistent=False)
         for s_, idxs in enumerate(self._SLICES):
@@ -585,7 +591,112 @@ class LossLpips(torch.nn.Module):
     def forward(self, prediction: Tensor, target: Tensor, global_step: int = 0) -> Tensor:
         if global_step < self.apply_after_step:
             return torch.zeros((), dtype=torch.float32, device=target.device)
+        if self._hip is not None:
+            return self.weight * self._hip(prediction.flatten(0, 1), target.flatten(0, 1), normalize=True).mean()
         return self.weight * self.distance(prediction.flatten(0, 1).float(), target.flatten(0, 1).float()).mean()
+
+
+class LpipsVgg(torch.nn.Module):
+    """lpips.LPIPS(net="vgg", version="0.1") in eval mode on the HIP kernels: forward(in0, in1, normalize=False) -> [N, 1, 1, 1], the call of
+    lpips.LPIPS.forward.  The definition is LossLpips.features / .distance (scaling layer on 2x - 1 when `normalize`, VGG-16 up to relu5_3,
+    unit-normalised taps, non-negative 1x1 heads, spatial mean, sum over the taps); `weights` is the state dict LossLpips reads.
+    The 13 convolutions run in the split operand class (vs_conv3x3_split_nhwc: f32 activations, f16 (hi, lo) weight pairs), the glue on
+    csrc/lpips.hip.  Their weights and the flipped, channel-transposed weights of the data gradient are packed ONCE, here, on `device`
+    (default: the current HIP device); calls are free of host synchronisation.  Differentiable in in0 and in1 (autograd.LpipsFn): each side
+    that needs a gradient keeps its 13 post-ReLU activations, 70.8 MB per 256 x 256 image (20.4 GB for 288 views).
+    Conventions, each pinned by tests/test_lpips_*.py: at a pixel where a tap's whole channel vector is 0 the normalisation's derivative is
+    the finite limit I / (r + eps) (torch autograd gives NaN there); max-pool ties go to the first maximum in row-major window order, as
+    torch's; the lpips heads' nn.Dropout is off (eval mode) -- the reference's training run has it active, and this is its expectation.
+    Inputs: [N, 3, H, W] on a HIP device, H and W multiples of 16; anything else raises ValueError (there is no CPU path)."""
+
+    def __init__(self, weights, device=None):
+        super().__init__()
+        from . import ops
+        if weights is None:
+            raise RuntimeError("LpipsVgg needs the state_dict of lpips.LPIPS(net='vgg'); it is never replaced by random weights")
+        sd = torch.load(weights, map_location="cpu") if isinstance(weights, (str, Path)) else dict(weights)
+        if not torch.cuda.is_available():
+            raise ValueError("LpipsVgg runs on the HIP kernels and needs a HIP device; use LossLpips(backend='torch') on the CPU")
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError(f"LpipsVgg needs a HIP device, got {dev}")
+        self.device = dev
+        self.convs, self.lins = [], []       # convs[k] = (forward weight, bias, data-gradient weight), k = 0..12 in VGG order
+
+        def pack(w: Tensor, cin_pad: int = 0):
+            w = w.float().contiguous()
+            if cin_pad > w.shape[-1]:
+                w = torch.nn.functional.pad(w, (0, cin_pad - w.shape[-1]))
+            return ops.split_pack_weight(w.to(dev), ops.split_scale_exp(w))      # the exponent from the host copy: no device read
+
+        for s_, idxs in enumerate(LossLpips._SLICES):
+            for j, li in enumerate(idxs):
+                w, b = sd[f"net.slice{s_ + 1}.{li}.weight"].detach().float().cpu(), sd[f"net.slice{s_ + 1}.{li}.bias"].detach().float()
+                assert tuple(w.shape) == (LossLpips._CHANNELS[s_][j + 1], LossLpips._CHANNELS[s_][j], 3, 3), (s_, li, tuple(w.shape))
+                first = s_ == 0 and j == 0
+                wf = pack(w.permute(0, 2, 3, 1), 32 if first else 0)                       # [Cout, 3, 3, Cin(32)]
+                wd = w.flip(2, 3).permute(1, 2, 3, 0)                                       # [Cin, 3, 3, Cout]
+                if first:
+                    wd = torch.nn.functional.pad(wd, (0, 0, 0, 0, 0, 0, 0, 32 - wd.shape[0]))  # 32 output channels, the last 29 zero
+                self.convs.append((wf, b.contiguous().to(dev), pack(wd)))
+            lin = sd.get(f"lin{s_}.model.1.weight", sd.get(f"lins.{s_}.model.1.weight"))
+            assert lin is not None and lin.shape[1] == LossLpips._CHANNELS[s_][-1]
+            self.lins.append(lin.detach().float().reshape(-1).contiguous().to(dev))
+        self._first = [0, 2, 4, 7, 10]         # index of each slice's first convolution
+        self._taps = [1, 3, 6, 9, 12]          # relu1_2, relu2_2, relu3_3, relu4_3, relu5_3
+
+    def taps(self, acts):
+        return [acts[k] for k in self._taps]
+
+    def features(self, x: Tensor, normalize: bool, keep_all: bool = True):
+        """The 13 post-ReLU activations (NHWC f32) of the VGG-16 trunk for images x [N, 3, H, W]; without keep_all only the five taps are
+        kept (the other entries are None), so a side that needs no gradient holds 32 MB per 256 x 256 image instead of 71 MB."""
+        from . import ops
+        h = ops.lpips_prep(x, normalize)
+        acts = []
+        for k, (wf, b, _) in enumerate(self.convs):
+            if k in self._first and k > 0:
+                h = ops.lpips_maxpool(h)
+            h = ops.conv3x3_nhwc(h, wf, b, relu_out=True)
+            acts.append(h if keep_all or k in self._taps else None)
+        return acts
+
+    def features_backward(self, acts, dtaps, g: Tensor, normalize: bool) -> Tensor:
+        """Image gradient [N, 3, H, W] from the heads' gradients dtaps (ReLU-masked, at ops.lpips_scale_log2) and the activations."""
+        from . import ops
+        grad = dtaps[4]                                        # w.r.t. conv5_3's pre-activation
+        for k in range(len(self.convs) - 1, -1, -1):
+            wd = self.convs[k][2]
+            if k in self._first:
+                grad = ops.conv3x3_nhwc(grad, wd, None)        # w.r.t. the slice's input: the pooled tensor or the prepared image
+                if k > 0:                                      # through the pool into the previous tap, + its head gradient, ReLU mask
+                    s_ = self._first.index(k)
+                    grad = ops.lpips_maxpool_backward(grad, acts[k - 1], dtaps[s_ - 1])
+            else:
+                grad = ops.conv3x3_nhwc(grad, wd, None, mask_by=acts[k - 1])
+        return ops.lpips_prep_backward(grad, g, normalize)
+
+    def _check(self, in0: Tensor, in1: Tensor):
+        if in0.shape != in1.shape or in0.dim() != 4 or in0.shape[1] != 3 or in0.shape[0] == 0:
+            raise ValueError(f"LPIPS takes two [N, 3, H, W] tensors of one shape, got {tuple(in0.shape)} and {tuple(in1.shape)}")
+        H, W = in0.shape[-2:]
+        if H % 16 or W % 16:
+            raise ValueError(f"LPIPS on the HIP kernels needs H and W that are multiples of 16 (four 2 x 2 max-pools), got {H} x {W}")
+        for t in (in0, in1):
+            if t.device != self.device:
+                raise ValueError(f"LpipsVgg was built on {self.device}; got an input on {t.device} (there is no CPU fallback)")
+
+    def forward(self, in0: Tensor, in1: Tensor, normalize: bool = False) -> Tensor:
+        from . import autograd as A
+        self._check(in0, in1)
+        return A.LpipsFn.apply(in0, in1, self, bool(normalize))
+
+
+@torch.no_grad()
+def compute_lpips(ground_truth: Tensor, predicted: Tensor, net: LpipsVgg) -> Tensor:
+    """LPIPS per image of [batch, 3, h, w] tensors in [0, 1], as metrics.py:37-44 computes it (lpips.LPIPS(net="vgg").forward(gt, pred,
+    normalize=True)[:, 0, 0, 0]) on the HIP kernels of `net`.  Returns a device tensor [batch] of predicted.dtype; no host synchronisation."""
+    return net(ground_truth, predicted, normalize=True)[:, 0, 0, 0].to(predicted.dtype)
 
 
 class LossScaler:

@@ -1494,3 +1494,92 @@ def ssim_backward(x: torch.Tensor, y: torch.Tensor, taps, cov_norm: float, c1: f
                                       L.ptr(dy), L.stream_ptr(dev))
     L.check(rc, "vs_ssim_backward")
     return dx, dy
+
+
+LPIPS_TAP_CHANNELS = (64, 128, 256, 512, 512)     # relu1_2, relu2_2, relu3_3, relu4_3, relu5_3
+
+
+def lpips_scale_log2(H: int, W: int) -> int:
+    """The power of two the LPIPS backward runs its data gradients at (vs_lpips_head_backward / vs_lpips_prep_backward): 2^8 over the
+    image's pixel count, which cancels the spatial mean of relu1_2 and keeps the split class's f16 (hi, lo) halves of the gradients normal."""
+    return max(0, (H * W - 1).bit_length()) + 8
+
+
+def _ptr_array(ts):
+    import ctypes
+    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def lpips_prep(img: torch.Tensor, normalize: bool) -> torch.Tensor:
+    """[N, 3, H, W] image -> [N, H, W, 32] f32 NHWC: optional 2x - 1, the scaling layer, channels 3..31 zero (vs_lpips_prep)."""
+    dev = L.require_device(img)
+    img = img.contiguous().float()
+    N, _, H, W = img.shape
+    out = torch.empty((N, H, W, 32), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.lib().vs_lpips_prep(L.ptr(img), N, H, W, int(normalize), L.ptr(out), L.stream_ptr(dev))
+    L.check(rc, "vs_lpips_prep")
+    return out
+
+
+def lpips_prep_backward(g32: torch.Tensor, g: torch.Tensor, normalize: bool) -> torch.Tensor:
+    """conv1_1's data gradient [N, H, W, 32] (at the scale of lpips_scale_log2) -> the image gradient [N, 3, H, W] (vs_lpips_prep_backward)."""
+    dev = L.require_device(g32, g)
+    N, H, W, _ = g32.shape
+    g = g.detach().reshape(N).contiguous().float()
+    out = torch.empty((N, 3, H, W), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.lib().vs_lpips_prep_backward(L.ptr(g32), L.ptr(g), N, H, W, int(normalize), lpips_scale_log2(H, W), L.ptr(out), L.stream_ptr(dev))
+    L.check(rc, "vs_lpips_prep_backward")
+    return out
+
+
+def lpips_maxpool(x: torch.Tensor) -> torch.Tensor:
+    """2 x 2 stride-2 max-pool of an NHWC f32 tensor (vs_lpips_maxpool)."""
+    dev = L.require_device(x)
+    N, H, W, C = x.shape
+    y = torch.empty((N, H // 2, W // 2, C), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.lib().vs_lpips_maxpool(L.ptr(x), N, H, W, C, L.ptr(y), L.stream_ptr(dev))
+    L.check(rc, "vs_lpips_maxpool")
+    return y
+
+
+def lpips_maxpool_backward(dy: torch.Tensor, x: torch.Tensor, g_add: Optional[torch.Tensor]) -> torch.Tensor:
+    """(x > 0) * (g_add + dy routed to the first maximum of each 2 x 2 window of x) (vs_lpips_maxpool_backward)."""
+    dev = L.require_device(dy, x, g_add)
+    N, H, W, C = x.shape
+    dx = torch.empty_like(x)
+    with torch.cuda.device(dev):
+        rc = L.lib().vs_lpips_maxpool_backward(L.ptr(dy), L.ptr(x), L.ptr(g_add), N, H, W, C, L.ptr(dx), L.stream_ptr(dev))
+    L.check(rc, "vs_lpips_maxpool_backward")
+    return dx
+
+
+def lpips_head_forward(taps0, taps1, lins) -> torch.Tensor:
+    """Per-image LPIPS distance [N] f32 from the five taps of both images (NHWC f32) and the five lin weights (vs_lpips_head_forward)."""
+    dev = L.require_device(*taps0, *taps1, *lins)
+    N, H, W, _ = taps0[0].shape
+    nbytes = L.check(L.lib().vs_lpips_workspace_bytes(N, H, W), "vs_lpips_workspace_bytes")
+    work = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    out = torch.empty(N, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.lib().vs_lpips_head_forward(_ptr_array(taps0), _ptr_array(taps1), _ptr_array(lins), N, H, W, L.ptr(work), L.ptr(out),
+                                           L.stream_ptr(dev))
+    L.check(rc, "vs_lpips_head_forward")
+    return out
+
+
+def lpips_head_backward(taps0, taps1, lins, g: torch.Tensor, need0: bool, need1: bool):
+    """dL/dtap (times the tap's ReLU mask, at the scale of lpips_scale_log2) for image 0 and / or image 1: two lists of five NHWC tensors
+    (None for a side not asked for) (vs_lpips_head_backward)."""
+    dev = L.require_device(*taps0, *taps1, *lins, g)
+    N, H, W, _ = taps0[0].shape
+    g = g.detach().reshape(N).contiguous().float()
+    d0 = [torch.empty_like(t) for t in taps0] if need0 else None
+    d1 = [torch.empty_like(t) for t in taps1] if need1 else None
+    with torch.cuda.device(dev):
+        rc = L.lib().vs_lpips_head_backward(_ptr_array(taps0), _ptr_array(taps1), _ptr_array(lins), L.ptr(g), N, H, W, lpips_scale_log2(H, W),
+                                            None if d0 is None else _ptr_array(d0), None if d1 is None else _ptr_array(d1), L.stream_ptr(dev))
+    L.check(rc, "vs_lpips_head_backward")
+    return d0, d1
