@@ -502,7 +502,10 @@ struct AttnArgsSplit {
 };
 
 // four consecutive columns n .. n + 3 of an f32 row written in the packed (hi, lo) layout of vs_split_pack_weight (gemm_common.h, store_split4)
+// The residuals x - hi are taken from the f32 values as given: no contraction with the producer of a .. d (an fma would subtract hi from
+// the unrounded product and move lo by one unit), so the packed image is bit-identical to packing the f32 output.
 __device__ __forceinline__ void store_split4_attn(float *row, int n, float a, float b, float c, float d) {
+#pragma clang fp contract(off)
     typedef _Float16 h2_ __attribute__((ext_vector_type(2)));
     typedef float f2_ __attribute__((ext_vector_type(2)));
     const h2_ h0 = __builtin_convertvector(f2_{a, b}, h2_), h1 = __builtin_convertvector(f2_{c, d}, h2_);
@@ -715,7 +718,8 @@ __global__ void __launch_bounds__(256, 2) attention_split_kernel(const AttnArgsS
             float *rowp = a.out + (b * a.q_batch_rows + qo) * a.ldo;
 #pragma unroll
             for (int db = 0; db < 4; ++db)
-                store_split4_attn(rowp, h * HD + db * 16 + g * 4, o[u][db][0] * inv, o[u][db][1] * inv, o[u][db][2] * inv, o[u][db][3] * inv);
+                store_split4_attn(rowp, h * HD + db * 16 + g * 4, __fmul_rn(o[u][db][0], inv), __fmul_rn(o[u][db][1], inv), __fmul_rn(o[u][db][2], inv),
+                                  __fmul_rn(o[u][db][3], inv));
         } else {
 #pragma unroll
             for (int db = 0; db < 4; ++db)
