@@ -67,6 +67,65 @@ def test_python_constants_mirror_the_header_enums():
     assert C.sizeof(_lib.VsRasterOut) == 6 * 8 + enums["VS_BUF_COUNT"] * 8
 
 
+def _header_text():
+    return open(os.path.join(ROOT, "include", "vicasplat_hip.h")).read()
+
+
+def test_every_prototype_of_the_header_is_bound_with_its_argument_list():
+    """The ctypes signatures are read from the header: every declared entry has restype and argtypes on the loaded library, as many
+    arguments as the prototype has parameters -- and nothing is left to ctypes' default conversion."""
+    from vicasplat_amd import _lib
+    L = _lib.lib()
+    txt = re.sub(r"/\*.*?\*/", "", _header_text(), flags=re.S)
+    protos = {m.group(1): m.group(2) for m in re.finditer(r"\b(vs_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", txt)}
+    assert set(protos) == _declared_symbols() and len(protos) == 78
+    for name, params in protos.items():
+        fn = getattr(L, name)
+        n = 0 if params.strip() == "void" else params.count(",") + 1
+        assert fn.argtypes is not None and len(fn.argtypes) == n, (name, fn.argtypes, n)
+        assert fn.restype in (C.c_int, C.c_int64, C.c_char_p), (name, fn.restype)
+    i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
+    # int vs_rope2d(void *tokens, const int64_t *pos, int32_t B, int32_t N, int32_t H, int32_t D, int64_t sB, int64_t sN, float base, float fwd,
+    #               int32_t dtype, vs_stream_t stream) -- as INTEGRATION.md prints it
+    assert L.vs_rope2d.restype is C.c_int
+    assert L.vs_rope2d.argtypes == [vp, vp, i32, i32, i32, i32, i64, i64, f32, f32, i32, vp]
+    # ... int32_t ldo, int64_t a_slice_stride, int64_t w_slice_stride, int64_t tap_out_stride, ..., void *workspace, int64_t workspace_bytes, ...
+    assert L.vs_gemm_wgrad.restype is C.c_int
+    assert L.vs_gemm_wgrad.argtypes == [vp, vp, vp, i32, i32, i32, i32, i32, i32, i64, i64, i64, vp, i32, i32, i32, vp, i64, i32, vp]
+    assert L.vs_ssim_workspace_bytes.restype is C.c_int64 and L.vs_ssim_workspace_bytes.argtypes == [i32] * 6
+    assert L.vs_raster_backward.argtypes == [C.POINTER(_lib.VsRasterIn), C.POINTER(_lib.VsRasterOut), C.POINTER(_lib.VsRasterGrads),
+                                             _lib.AllocFn, vp, vp]
+
+
+def test_header_parser_refuses_what_it_does_not_know():
+    """An unknown type or an unparsable prototype is an error that quotes the prototype, never a silently defaulted argument."""
+    import pytest
+    from vicasplat_amd import _lib
+    ok = _lib.parse_header("/* c */ int vs_x(const float *a, int64_t n, vs_stream_t stream);\nint64_t vs_y(int32_t n);")
+    assert ok["vs_x"] == (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p], True) and ok["vs_y"] == (C.c_int64, [C.c_int32], False)
+    with pytest.raises(ValueError, match=r"unsigned short n.*vs_bad"):
+        _lib.parse_header("int vs_bad(const float *a, unsigned short n, vs_stream_t stream);")
+    with pytest.raises(ValueError, match="vs_bad"):
+        _lib.parse_header("struct Foo vs_bad(int32_t n);")
+    with pytest.raises(ValueError, match="vs_bad"):
+        _lib.parse_header("int vs_bad(int32_t n;")
+
+
+def test_struct_mirrors_follow_the_header_field_by_field():
+    """VsRasterIn / VsRasterOut / VsRasterGrads are hand-written ctypes mirrors: same field names in the same order as the header."""
+    from vicasplat_amd import _lib
+    txt = re.sub(r"/\*.*?\*/", "", _header_text(), flags=re.S)
+    for name in ("VsRasterIn", "VsRasterOut", "VsRasterGrads"):
+        body = re.search(r"typedef\s+struct\s+%s\s*\{(.*?)\}\s*%s\s*;" % (name, name), txt, flags=re.S).group(1)
+        fields = []
+        for decl in body.split(";"):
+            if decl.strip():
+                first, *more = decl.split(",")       # `int32_t width, height`: one declaration, two fields
+                fields += [re.search(r"(\w+)\s*(?:\[\w+\])?\s*$", d).group(1) for d in [first] + more]
+        assert fields == [f[0] for f in getattr(_lib, name)._fields_], (name, fields)
+    assert len(_lib.VsRasterIn._fields_) == 20 and len(_lib.VsRasterGrads._fields_) == 9
+
+
 def test_head_tail_refuses_an_input_that_is_not_a_relu_output():
     """the fused tail of a DPT head masks its input gradient by t > 0 and tells the producer to skip its ReLU backward -- only
     valid behind Conv3x3Fn(..., relu_out=True).  The producer is identified by its autograd node; anything else must not take the route."""

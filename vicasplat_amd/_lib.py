@@ -7,16 +7,19 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import subprocess
 import threading
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
+_HEADER = os.path.join(_HERE, "..", "include", "vicasplat_hip.h")     # the one statement of every signature (parse_header)
 _SO = os.environ.get("VICASPLAT_HIP_LIB") or os.path.join(_HERE, "libvicasplat_hip.so")   # (override: A/B runs of two builds)
 _lock = threading.Lock()
 ABI_VERSION = 10    # == vs_abi_version() of csrc/api.hip; INTEGRATION.md lists the entries of every version
 _lib = None
+_entries: dict = {}    # name -> (bound function, takes the stream as its last argument), filled by _load() from the header
 
 VS_BUF_GEOM, VS_BUF_RECT, VS_BUF_CLAMPED, VS_BUF_TILE_RANGES, VS_BUF_TILE_CURSOR, VS_BUF_KEYS, VS_BUF_POINT_LIST, \
     VS_BUF_SORT_SCRATCH, VS_BUF_FINAL_T, VS_BUF_N_CONTRIB, VS_BUF_MISC, VS_BUF_DEPTH, VS_BUF_CHECKPOINT, VS_BUF_COUNT = range(14)
@@ -60,14 +63,54 @@ def build(force: bool = False) -> str:
     src_dir = os.path.join(_HERE, "csrc")
     newest = max(os.path.getmtime(os.path.join(src_dir, f)) for f in os.listdir(src_dir)
                  if f.endswith((".hip", ".h", "Makefile")))
-    newest = max(newest, os.path.getmtime(os.path.join(_HERE, "..", "include", "vicasplat_hip.h")))
+    newest = max(newest, os.path.getmtime(_HEADER))
     if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < newest:
         subprocess.check_call(["make", "-C", src_dir, "-j8"], stdout=subprocess.DEVNULL)
     return _SO
 
 
+_C_TYPES = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t,
+            "vs_stream_t": C.c_void_p, "VsAllocFn": AllocFn}
+_C_RETURNS = {"int": C.c_int, "int64_t": C.c_int64, "const char *": C.c_char_p}
+_STRUCTS = {"VsRasterIn": VsRasterIn, "VsRasterOut": VsRasterOut, "VsRasterGrads": VsRasterGrads}
+
+
+def parse_header(text: str) -> dict:
+    """{name: (restype, [argtypes], takes_stream)} of every prototype in the text of include/vicasplat_hip.h.  The header is the one place
+    where a signature is written down; a prototype or a type outside its small vocabulary raises with the prototype's text (ctypes'
+    default conversion would truncate or shift the arguments silently)."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*|^\s*#[^\n]*", "", text, flags=re.S | re.M)
+    text = re.sub(r'extern\s+"C"\s*\{|\b(?:typedef\s+struct|enum)\b[^{;]*\{[^}]*\}[^;]*;|\btypedef\b[^;{]*;', "", text)
+    sigs = {}
+    for proto in (" ".join(p.split()) for p in text.split(";")):
+        if proto in ("", "}"):
+            continue
+        m = re.fullmatch(r"(.+?)\b(vs_\w+) ?\((.*)\)", proto)
+        ret = m and m.group(1).strip()
+        if not m or ret not in _C_RETURNS:
+            raise ValueError(f"vicasplat_hip.h: cannot parse the prototype `{proto}`")
+        params = [] if m.group(3).strip() == "void" else [p.strip() for p in m.group(3).split(",")]
+        argtypes = []
+        for p in params:
+            base = re.sub(r"\bconst\b|\w+$", "", p).replace(" ", "")      # the type without qualifiers and without the parameter's name
+            if base.endswith("*"):
+                argtypes.append(C.POINTER(_STRUCTS[base[:-1]]) if base[:-1] in _STRUCTS else C.c_void_p)
+            elif base in _C_TYPES:
+                argtypes.append(_C_TYPES[base])
+            else:
+                raise ValueError(f"vicasplat_hip.h: unknown type `{p}` in the prototype `{proto}`")
+        sigs[m.group(2)] = (_C_RETURNS[ret], argtypes, bool(params) and params[-1].startswith("vs_stream_t "))
+    return sigs
+
+
 def lib() -> C.CDLL:
-    """Load the C-ABI library; raise loudly when it is absent (no silent fallback)."""
+    """The loaded C-ABI library (see _load)."""
+    return _lib if _lib is not None else _load()
+
+
+def _load() -> C.CDLL:
+    """Load the C-ABI library and bind every entry point to the signature the header declares; raise loudly when it is absent (no silent
+    fallback)."""
     global _lib
     with _lock:
         if _lib is None:
@@ -76,158 +119,27 @@ def lib() -> C.CDLL:
                     f"{_SO} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                     "(vicasplat_amd has no CPU / PyTorch fallback path)")
             L = C.CDLL(_SO)
-            L.vs_last_error.restype = C.c_char_p
-            L.vs_abi_version.restype = C.c_int
-            if L.vs_abi_version() != ABI_VERSION:     # the ctypes mirrors of the structs below are for exactly this layout
+            if L.vs_abi_version() != ABI_VERSION:     # the ctypes mirrors of the structs above are for exactly this layout
                 raise RuntimeError(f"{_SO} has ABI version {L.vs_abi_version()}, this package needs {ABI_VERSION}: rebuild it (python -c 'import __graft_entry__ as g; g.build()')")
-            L.vs_raster_forward.restype = C.c_int64
-            L.vs_raster_forward.argtypes = [C.POINTER(VsRasterIn), C.POINTER(VsRasterOut), AllocFn, C.c_void_p, C.c_void_p]
-            L.vs_rope2d.restype = C.c_int
-            L.vs_rope2d.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
-                                    C.c_int64, C.c_float, C.c_float, C.c_int32, C.c_void_p]
-            i32, i64, vp, f32 = C.c_int32, C.c_int64, C.c_void_p, C.c_float
-            L.vs_range_check.restype = C.c_int
-            L.vs_range_check.argtypes = [vp, i64, i32, i64, i32, f32, vp, i32, vp]
-            L.vs_layernorm_mod.restype = C.c_int
-            L.vs_layernorm_mod.argtypes = [vp, i64, vp, vp, vp, vp, i32, i32, vp, i64, i32, i32, i32, f32, i32, i32, i32, vp]
-            L.vs_gemm_bias_act.restype = C.c_int
-            L.vs_gemm_bias_act.argtypes = [vp, vp, vp, vp, vp] + [i32] * 16 + [vp]
-            L.vs_rope_qk.restype = C.c_int
-            L.vs_rope_qk.argtypes = [vp, i64, i32, i32, i32, vp, vp, f32, f32, i32, vp]
-            L.vs_attention.restype = C.c_int
-            L.vs_attention.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i64, i64, i32, i32, i32, i32, vp, vp, f32, i32, vp]
-            L.vs_gaussian_adapter_backward.restype = C.c_int
-            L.vs_gaussian_adapter_backward.argtypes = [vp, i32, vp, i32, i64, i32, vp, i32, f32, f32, f32, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp]
-            L.vs_gaussian_adapter.restype = C.c_int
-            L.vs_gaussian_adapter.argtypes = [vp, i64, i64, vp, i64, i64, i32, i64, i32, vp, i32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp]
-            L.vs_rope_qk_dir.restype = C.c_int
-            L.vs_rope_qk_dir.argtypes = [vp, i64, i32, i32, i32, vp, vp, f32, f32, f32, i32, vp]
-            L.vs_attention_lse.restype = C.c_int
-            L.vs_attention_lse.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i64, i64, i32, i32, i32, i32, vp, vp, f32, i32, vp, vp]
-            L.vs_attention_backward.restype = C.c_int
-            L.vs_attention_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i64, i64, i32, i32, i32, i32, i32,
-                                                i32, i32, i32, vp, vp, i32, f32, i32, vp]
-            L.vs_attention_backward16.restype = C.c_int
-            L.vs_attention_backward16.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i64, i64, i32, i32, i32, i32, i32,
-                                                  i32, i32, i32, vp, f32, i32, vp]
-            L.vs_upsample2x_backward_nhwc.restype = C.c_int
-            L.vs_upsample2x_backward_nhwc.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
-            L.vs_relu_mask16.restype = C.c_int
-            L.vs_relu_mask16.argtypes = [vp, vp, i64, vp]
-            L.vs_relu_mask16_to.restype = C.c_int
-            L.vs_relu_mask16_to.argtypes = [vp, vp, vp, i64, vp]
-            L.vs_gemm_splitk_accumulate.restype = C.c_int
-            L.vs_gemm_splitk_accumulate.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]
-            L.vs_gemm_taps_accumulate.restype = C.c_int
-            L.vs_gemm_taps_accumulate.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i64, vp, i32, i32, i32, vp]
-            L.vs_gemm_wgrad.restype = C.c_int
-            L.vs_gemm_wgrad.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i64, i64, i64, vp, i32, i32, i32, vp, i64, i32, vp]
-            L.vs_conv3x3_wgrad_tn.restype = C.c_int
-            L.vs_conv3x3_wgrad_tn.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i64, i32, vp]
-            L.vs_gemm_wgrad_tn.restype = C.c_int
-            L.vs_gemm_wgrad_tn.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i64, i32, vp]
-            L.vs_gemm_resid.restype = C.c_int
-            L.vs_gemm_resid.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
-            L.vs_transpose16.restype = C.c_int
-            L.vs_transpose16.argtypes = [vp, i64, vp, i64, i32, i32, i32, vp]
-            L.vs_transpose16_ex.restype = C.c_int
-            L.vs_transpose16_ex.argtypes = [vp, i64, vp, i64, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, i64, vp]
-            L.vs_colsum.restype = C.c_int
-            L.vs_colsum.argtypes = [vp, i64, vp, i32, i32, i32, vp]
-            L.vs_gated_resid.restype = C.c_int
-            L.vs_gated_resid.argtypes = [vp, vp, i64, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp]
-            L.vs_gated_resid_backward.restype = C.c_int
-            L.vs_gated_resid_backward.argtypes = [vp, vp, i64, vp, i32, vp, i64, vp, i32, i32, i32, i32, i32, i32, vp]
-            L.vs_gelu16.restype = C.c_int
-            L.vs_gelu16.argtypes = [vp, vp, i64, i32, vp]
-            L.vs_gelu_backward.restype = C.c_int
-            L.vs_gelu_backward.argtypes = [vp, vp, vp, i64, i32, vp]
-            L.vs_layernorm_backward.restype = C.c_int
-            L.vs_layernorm_backward.argtypes = [vp, i64, i32, vp, i64, vp, vp, vp, i32, i32, vp, i64, i32, vp, vp, vp, vp, i32, i32, f32,
-                                                i32, i32, i32, vp]
-            L.vs_layernorm_backward_ex.restype = C.c_int
-            L.vs_layernorm_backward_ex.argtypes = [vp, i64, i32, vp, i64, vp, vp, vp, i32, i32, vp, i64, vp, i64, vp, i64, i32, vp, vp, vp, vp,
-                                                   i32, i32, f32, i32, i32, i32, vp]
-            L.vs_gemm_qkv_rope.restype = C.c_int
-            L.vs_gemm_qkv_rope.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32,
-                                           C.c_float, C.c_float, vp]
-            L.vs_conv7x7_rgb_nhwc.restype = C.c_int
-            L.vs_conv7x7_rgb_nhwc.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
-            L.vs_conv3x3_nhwc.restype = C.c_int
-            L.vs_conv3x3_nhwc.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
-            L.vs_linear_f32.restype = C.c_int
-            L.vs_linear_f32.argtypes = [vp, i64, vp, i64, vp, vp, i64, i32, i32, i32, i32, vp]
-            L.vs_silu_cast.restype = C.c_int
-            L.vs_silu_cast.argtypes = [vp, vp, i64, i32, vp]
-            L.vs_conv3x3_head1x1_nhwc.restype = C.c_int
-            L.vs_conv3x3_head1x1_nhwc.argtypes = [vp, vp, vp, vp, vp, vp] + [i32] * 11 + [vp]
-            L.vs_split_pack_weight.restype = C.c_int
-            L.vs_split_pack_weight.argtypes = [vp, i64, vp, i64, i32, i32, i32, vp]
-            L.vs_gemm_split.restype = C.c_int
-            L.vs_gemm_split.argtypes = [vp, vp, f32, vp, vp, vp, vp] + [i32] * 15 + [vp, vp, i32, f32, f32, vp]
-            L.vs_gemm_split_packed.restype = C.c_int
-            L.vs_gemm_split_packed.argtypes = [vp, vp, f32, vp, vp, vp, vp] + [i32] * 15 + [vp, vp, i32, f32, f32, vp]
-            L.vs_conv3x3_split_nhwc.restype = C.c_int
-            L.vs_conv3x3_split_nhwc.argtypes = [vp, vp, f32, vp, vp, vp] + [i32] * 8 + [vp]
-            L.vs_conv3x3_split_res2_nhwc.restype = C.c_int
-            L.vs_conv3x3_split_res2_nhwc.argtypes = [vp, vp, f32, vp, vp, vp, vp] + [i32] * 8 + [vp]
-            L.vs_conv3x3_head1x1_split_nhwc.restype = C.c_int
-            L.vs_conv3x3_head1x1_split_nhwc.argtypes = [vp, vp, f32, vp, vp, f32, vp, vp] + [i32] * 8 + [vp]
-            L.vs_conv3x3_head_dot_split_nhwc.restype = C.c_int
-            L.vs_conv3x3_head_dot_split_nhwc.argtypes = [vp, vp, f32, vp, vp, vp, vp] + [i32] * 8 + [vp]
-            L.vs_conv7x7_rgb_split_nhwc.restype = C.c_int
-            L.vs_conv7x7_rgb_split_nhwc.argtypes = [vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-            L.vs_conv7x7_rgb_split_up_nhwc.restype = C.c_int
-            L.vs_conv7x7_rgb_split_up_nhwc.argtypes = [vp, vp, f32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-            L.vs_upsample2x_nhwc.restype = C.c_int
-            L.vs_upsample2x_nhwc.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-            L.vs_probe_mfma_rate.restype = C.c_int
-            L.vs_probe_mfma_rate.argtypes = [vp, vp, i32, C.POINTER(C.c_double), vp]
-            L.vs_transpose_f32.restype = C.c_int
-            L.vs_transpose_f32.argtypes = [vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]
-            L.vs_gemm_wgrad_split_atn.restype = C.c_int
-            L.vs_gemm_wgrad_split_atn.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i64, i32, vp]
-            L.vs_conv3x3_wgrad_split_atn.restype = C.c_int
-            L.vs_conv3x3_wgrad_split_atn.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i64, i32, vp]
-            L.vs_transpose_pack_split.restype = C.c_int
-            L.vs_transpose_pack_split.argtypes = [vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]
-            L.vs_split16.restype = C.c_int
-            L.vs_split16.argtypes = [vp, i64, vp, vp, i64, i64, i32, vp]
-            L.vs_attention_backward_split.restype = C.c_int
-            L.vs_attention_backward_split.argtypes = [vp] * 15 + [i32, i32, i32, i32, i64, i64] + [i32] * 9 + [vp, vp, i32, f32, vp]
-            for nm, at in (("vs_gelu_f32", [vp, vp, i64, vp]), ("vs_gelu_backward_f32", [vp, vp, vp, i64, vp]), ("vs_relu_mask_f32", [vp, vp, vp, i64, vp]),
-                           ("vs_gated_resid_f32", [vp, vp, i64, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
-                           ("vs_gated_resid_backward_f32", [vp, vp, i64, vp, i32, vp, i64, vp, i32, i32, i32, i32, i32, vp]),
-                           ("vs_upsample2x_backward_f32_nhwc", [vp, vp, i32, i32, i32, i32, vp]),
-                           ("vs_head1x1_backward_split", [vp, i64, vp, vp, i32, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
-                           ("vs_head1x1_backward16", [vp, i64, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp]),
-                           ("vs_conv3x3_wgrad_split_stream", [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
-                           ("vs_stem7x7_up_split_stream", [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
-                           ("vs_im2col7x7_rgb", [vp, vp, i32, i32, i32, i32, i32, vp])):
-                getattr(L, nm).restype = C.c_int
-                getattr(L, nm).argtypes = at
-            L.vs_ssim_workspace_bytes.restype = i64
-            L.vs_ssim_workspace_bytes.argtypes = [i32] * 6
-            L.vs_ssim_forward.restype = C.c_int
-            L.vs_ssim_forward.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, f32, f32, f32, i32, vp, vp, vp, vp]
-            L.vs_ssim_backward.restype = C.c_int
-            L.vs_ssim_backward.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, f32, f32, f32, i32, vp, vp, vp, vp, vp]
-            L.vs_lpips_workspace_bytes.restype = i64
-            L.vs_lpips_workspace_bytes.argtypes = [i32] * 3
-            for nm, at in (("vs_lpips_prep", [vp, i32, i32, i32, i32, vp, vp]),
-                           ("vs_lpips_prep_backward", [vp, vp, i32, i32, i32, i32, i32, vp, vp]),
-                           ("vs_lpips_maxpool", [vp, i32, i32, i32, i32, vp, vp]),
-                           ("vs_lpips_maxpool_backward", [vp, vp, vp, i32, i32, i32, i32, vp, vp]),
-                           ("vs_lpips_head_forward", [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
-                           ("vs_lpips_head_backward", [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp])):
-                getattr(L, nm).restype = C.c_int
-                getattr(L, nm).argtypes = at
-            if hasattr(L, "vs_raster_backward"):
-                L.vs_raster_backward.restype = C.c_int
-                L.vs_raster_backward.argtypes = [C.POINTER(VsRasterIn), C.POINTER(VsRasterOut), C.POINTER(VsRasterGrads),
-                                                 AllocFn, C.c_void_p, C.c_void_p]
+            with open(_HEADER) as f:
+                sigs = parse_header(f.read())
+            for name, (restype, argtypes, takes_stream) in sigs.items():
+                fn = getattr(L, name)
+                fn.restype, fn.argtypes = restype, argtypes
+                _entries[name] = (fn, takes_stream)
             _lib = L
     return _lib
+
+
+def call(name: str, dev: torch.device, *args):
+    """Run the entry point `name` on `dev`: on the device's current stream (passed as the last argument where the header declares a
+    vs_stream_t there), raising with the entry's own name and the library's message on a negative return.  Returns the entry's value."""
+    if _lib is None:
+        _load()
+    fn, takes_stream = _entries[name]
+    with torch.cuda.device(dev):
+        rc = fn(*args, torch.cuda.current_stream(dev).cuda_stream) if takes_stream else fn(*args)
+    return rc if rc >= 0 else check(rc, name)
 
 
 def check(rc: int, what: str) -> int:

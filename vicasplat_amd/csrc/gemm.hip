@@ -827,6 +827,26 @@ __global__ void __launch_bounds__(256) splitk_reduce_t_kernel(const float *__res
     }
 }
 
+// Host-side plumbing shared by the weight-gradient entry points.
+// Identity row maps of an M x N product: no output / input row grouping, one gate group.
+void identity_row_maps(GemmArgs &g, int M, int N) {
+    g.grp_in = M; g.grp_out = M; g.gate_rows = M; g.gate_ld = N; g.a_grp_in = M; g.a_grp_out = M;
+}
+
+// Validates a split-K workspace (`given` bytes where `need` are required) and attaches it; null: the slices meet through f32 atomics.
+int attach_workspace(const char *fn, GemmArgs &g, void *ws, long long given, long long need) {
+    g.partials = nullptr;
+    if (!ws) return 0;
+    VS_CHECK(given >= need, "%s: workspace of %lld bytes given, %lld needed", fn, given, need);
+    VS_CHECK((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: workspace must be 16-byte aligned", fn);
+    g.partials = (float *)ws;
+    return 0;
+}
+
+// Second stage of a workspace launch (defined behind vs_gemm_wgrad_tn).
+void launch_splitk_reduce(const float *ws, float *out, int M, int N, int ntaps, int ks, long long ldo, long long tap_out_stride, int accumulate,
+                          hipStream_t stream, bool transposed = false);
+
 // Weight-gradient launches (split-K, optionally tap-fused): 256x256 tiles on the phase-interleaved main loop when the
 // output is made of whole 256-tiles and every K slice is an even number (>= 2) of 64-wide K tiles; 128x128 tiles otherwise.
 // With a workspace of ksplit * ntaps * M * N floats the slices store partial tiles and a second kernel sums them; without
@@ -837,13 +857,8 @@ int launch_wgrad(GemmArgs &g, int ksplit, float *ws, long long ws_bytes, int acc
     const bool big = g.M % 256 == 0 && g.N % 256 == 0 && g.K % (128 * ksplit) == 0;
     const int slices = big ? ksplit : (ksplit > 1 ? ksplit : 2);  // gemm_kernel always runs >= 2 slices in this mode
     const long long need = (long long)slices * ntaps * g.M * g.N * (long long)sizeof(float);
-    g.partials = nullptr;
-    if (ws) {
-        if (ws_bytes < need) { vs::set_error("weight-gradient GEMM: workspace of %lld bytes given, %lld needed", ws_bytes, need); return -1; }
-        if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) { vs::set_error("weight-gradient GEMM: workspace must be 16-byte aligned"); return -1; }
-        g.partials = ws;
-    }
-    int rc = 0;
+    int rc = attach_workspace("weight-gradient GEMM", g, ws, ws_bytes, need);
+    if (rc) return rc;
     if (big) {
         g.ksplit = ksplit;
         const long long nwg = (long long)(g.M / 256) * (g.N / 256) * ntaps * ksplit;
@@ -857,11 +872,7 @@ int launch_wgrad(GemmArgs &g, int ksplit, float *ws, long long ws_bytes, int acc
         rc = launch_mi<BF16, 4>(g, 2, stream);
     }
     if (rc || !ws) return rc;
-    const bool v4 = g.N % 4 == 0 && g.ldo % 4 == 0 && g.tap_out_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(g.out) & 15) == 0;
-    const long long items = (long long)ntaps * g.M * (v4 ? g.N / 4 : g.N);
-    const dim3 grid((unsigned)((items + 255) / 256));
-    if (v4) hipLaunchKernelGGL(splitk_reduce_kernel<4>, grid, dim3(256), 0, stream, ws, (float *)g.out, g.M, g.N, ntaps, slices, (long long)g.ldo, g.tap_out_stride, accumulate);
-    else hipLaunchKernelGGL(splitk_reduce_kernel<1>, grid, dim3(256), 0, stream, ws, (float *)g.out, g.M, g.N, ntaps, slices, (long long)g.ldo, g.tap_out_stride, accumulate);
+    launch_splitk_reduce(ws, (float *)g.out, g.M, g.N, ntaps, slices, g.ldo, g.tap_out_stride, accumulate, stream);
     return 0;
 }
 
@@ -990,23 +1001,33 @@ extern "C" int vs_split_pack_weight(const float *w, int64_t ldw, void *out, int6
 // out = epilogue(acc_scale * (A Wp^T) + bias): A [M, K] f32 activations, Wp = vs_split_pack_weight image of the f32 weight (acc_scale =
 // 2^-scale_exp), every output f32.  Epilogues 0 / 3 store, 1 exact-erf GELU, 2 gated residual update (resid null: in place), 5 x GELU'(resid), 4 packed
 // q|k|v with RoPE (pos / kind / C / bases as vs_gemm_qkv_rope).  Row maps, gate and strides (in floats) as vs_gemm_bias_act.
+namespace {
+int gemm_split_entry(const char *fn, int a_packed, const void *A, const void *Wp, float acc_scale, const float *bias, float *out, const float *gate,
+                     const float *resid, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldw, int32_t ldo, int32_t epilogue, int32_t grp_in,
+                     int32_t grp_out, int32_t grp_off, int32_t gate_rows, int32_t gate_ld, int32_t a_grp_in, int32_t a_grp_out, int32_t a_grp_off,
+                     const int32_t *pos, const uint8_t *kind, int32_t C, float base2d, float theta1d, vs_stream_t stream_) {
+    const int out_packed = (epilogue & 16) ? 1 : 0;      // + 16: packed (hi, lo) output (epilogues 0 / 1 / 3: the A operand of vs_gemm_split_packed; 4: q | k | v for vs_attention dtype 4 + 32)
+    epilogue &= ~16;
+    VS_CHECK(epilogue >= 0 && epilogue <= (a_packed ? 4 : 5), "%s: unknown epilogue %d", fn, epilogue);      // epilogue 5 reads A as f32: refused for a packed A
+    VS_CHECK(epilogue != 5 || (resid && !bias && !gate && !out_packed && grp_in == 0 && K % 64 == 0), "%s: epilogue 5 (x GELU'(z)) needs z in `resid` (the layout of out), no bias / gate / row map / packed output, K %% 64 == 0", fn);
+    VS_CHECK(!out_packed || ((epilogue == 0 || epilogue == 1 || epilogue == 3 || epilogue == 4) && N % 64 == 0 && ldo % 32 == 0 && ((uintptr_t)out & 127) == 0),
+             "%s: a packed output needs epilogue 0 / 1 / 3 / 4, N %% 64 == 0, ldo %% 32 == 0 and a 128-byte aligned buffer", fn);
+    VS_CHECK(epilogue != 4 || (pos && C > 0 && C % 64 == 0 && N >= 2 * C && N % 64 == 0 && base2d > 0.f && theta1d > 0.f),
+             "%s: the RoPE epilogue needs pos, C %% 64 == 0, N >= 2C, positive bases", fn);
+    VS_CHECK(acc_scale > 0.f, "%s: acc_scale must be positive", fn);
+    return gemm_entry(fn, A, Wp, bias, out, gate, resid, M, N, K, lda, ldw, ldo, epilogue, 4, grp_in, grp_out, grp_off, gate_rows,
+                      gate_ld, a_grp_in, a_grp_out, a_grp_off, epilogue == 4 ? pos : nullptr, epilogue == 4 ? kind : nullptr, C, base2d, theta1d,
+                      (hipStream_t)stream_, acc_scale, a_packed, out_packed);
+}
+}  // namespace
+
 extern "C" int vs_gemm_split(const float *A, const void *Wp, float acc_scale, const float *bias, float *out, const float *gate, const float *resid,
                              int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldw, int32_t ldo, int32_t epilogue, int32_t grp_in,
                              int32_t grp_out, int32_t grp_off, int32_t gate_rows, int32_t gate_ld, int32_t a_grp_in, int32_t a_grp_out,
                              int32_t a_grp_off, const int32_t *pos, const uint8_t *kind, int32_t C, float base2d, float theta1d,
                              vs_stream_t stream_) {
-    const int out_packed = (epilogue & 16) ? 1 : 0;      // + 16: packed (hi, lo) output (epilogues 0 / 1 / 3: the A operand of vs_gemm_split_packed; 4: q | k | v for vs_attention dtype 4 + 32)
-    epilogue &= ~16;
-    VS_CHECK(epilogue >= 0 && epilogue <= 5, "vs_gemm_split: unknown epilogue %d", epilogue);
-    VS_CHECK(epilogue != 5 || (resid && !bias && !gate && !out_packed && grp_in == 0 && K % 64 == 0), "vs_gemm_split: epilogue 5 (x GELU'(z)) needs z in `resid` (the layout of out), no bias / gate / row map / packed output, K %% 64 == 0");
-    VS_CHECK(!out_packed || ((epilogue == 0 || epilogue == 1 || epilogue == 3 || epilogue == 4) && N % 64 == 0 && ldo % 32 == 0 && ((uintptr_t)out & 127) == 0),
-             "vs_gemm_split: a packed output needs epilogue 0 / 1 / 3 / 4, N %% 64 == 0, ldo %% 32 == 0 and a 128-byte aligned buffer");
-    VS_CHECK(epilogue != 4 || (pos && C > 0 && C % 64 == 0 && N >= 2 * C && N % 64 == 0 && base2d > 0.f && theta1d > 0.f),
-             "vs_gemm_split: the RoPE epilogue needs pos, C %% 64 == 0, N >= 2C, positive bases");
-    VS_CHECK(acc_scale > 0.f, "vs_gemm_split: acc_scale must be positive");
-    return gemm_entry("vs_gemm_split", A, Wp, bias, out, gate, resid, M, N, K, lda, ldw, ldo, epilogue, 4, grp_in, grp_out, grp_off, gate_rows,
-                      gate_ld, a_grp_in, a_grp_out, a_grp_off, epilogue == 4 ? pos : nullptr, epilogue == 4 ? kind : nullptr, C, base2d, theta1d,
-                      (hipStream_t)stream_, acc_scale, 0, out_packed);
+    return gemm_split_entry("vs_gemm_split", 0, A, Wp, acc_scale, bias, out, gate, resid, M, N, K, lda, ldw, ldo, epilogue, grp_in, grp_out, grp_off,
+                            gate_rows, gate_ld, a_grp_in, a_grp_out, a_grp_off, pos, kind, C, base2d, theta1d, stream_);
 }
 
 // vs_gemm_split with the A operand ALREADY packed (Ap = the vs_split_pack_weight image, scale_exp 0, of the f32 activation matrix; lda in
@@ -1016,17 +1037,8 @@ extern "C" int vs_gemm_split_packed(const void *Ap, const void *Wp, float acc_sc
                                     int32_t grp_out, int32_t grp_off, int32_t gate_rows, int32_t gate_ld, int32_t a_grp_in, int32_t a_grp_out,
                                     int32_t a_grp_off, const int32_t *pos, const uint8_t *kind, int32_t C, float base2d, float theta1d,
                                     vs_stream_t stream_) {
-    const int out_packed = (epilogue & 16) ? 1 : 0;      // + 16: packed (hi, lo) output (epilogues 0 / 1 / 3: the A operand of vs_gemm_split_packed; 4: q | k | v for vs_attention dtype 4 + 32)
-    epilogue &= ~16;
-    VS_CHECK(epilogue >= 0 && epilogue <= 4, "vs_gemm_split_packed: unknown epilogue %d", epilogue);
-    VS_CHECK(!out_packed || ((epilogue == 0 || epilogue == 1 || epilogue == 3 || epilogue == 4) && N % 64 == 0 && ldo % 32 == 0 && ((uintptr_t)out & 127) == 0),
-             "vs_gemm_split_packed: a packed output needs epilogue 0 / 1 / 3 / 4, N %% 64 == 0, ldo %% 32 == 0 and a 128-byte aligned buffer");
-    VS_CHECK(epilogue != 4 || (pos && C > 0 && C % 64 == 0 && N >= 2 * C && N % 64 == 0 && base2d > 0.f && theta1d > 0.f),
-             "vs_gemm_split_packed: the RoPE epilogue needs pos, C %% 64 == 0, N >= 2C, positive bases");
-    VS_CHECK(acc_scale > 0.f, "vs_gemm_split_packed: acc_scale must be positive");
-    return gemm_entry("vs_gemm_split_packed", Ap, Wp, bias, out, gate, resid, M, N, K, lda, ldw, ldo, epilogue, 4, grp_in, grp_out, grp_off, gate_rows,
-                      gate_ld, a_grp_in, a_grp_out, a_grp_off, epilogue == 4 ? pos : nullptr, epilogue == 4 ? kind : nullptr, C, base2d, theta1d,
-                      (hipStream_t)stream_, acc_scale, 1, out_packed);
+    return gemm_split_entry("vs_gemm_split_packed", 1, Ap, Wp, acc_scale, bias, out, gate, resid, M, N, K, lda, ldw, ldo, epilogue, grp_in, grp_out,
+                            grp_off, gate_rows, gate_ld, a_grp_in, a_grp_out, a_grp_off, pos, kind, C, base2d, theta1d, stream_);
 }
 
 // Weight-gradient GEMM: out32[t][M,N] += A[M,K] (W + shift[t])[N,K]^T for t < max(ntaps, 1), the K range cut into `ksplit` slices
@@ -1056,7 +1068,7 @@ extern "C" int vs_gemm_wgrad(const void *A, const void *W, float *out, int32_t M
     GemmArgs g;
     g.A = A; g.W = W; g.out = out;
     g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = ldw; g.ldo = ldo;
-    g.grp_in = M; g.grp_out = M; g.gate_rows = M; g.gate_ld = N; g.a_grp_in = M; g.a_grp_out = M;
+    identity_row_maps(g, M, N);
     g.ntaps = ntaps; g.tap_out_stride = ntaps > 0 ? tap_out_stride : 0;
     g.a_slice_stride = a_slice_stride; g.w_slice_stride = w_slice_stride;
     VS_CHECK(a_slice_stride >= 0 && w_slice_stride >= 0, "vs_gemm_wgrad: negative slice stride");
@@ -1092,28 +1104,36 @@ extern "C" int vs_gemm_wgrad_tn(const void *A, const void *W, float *out, int32_
     GemmArgs g;
     g.A = A; g.W = W; g.out = out;
     g.M = M; g.N = N; g.K = (int)Kpad; g.lda = lda; g.ldw = ldw; g.ldo = ldo;
-    g.grp_in = M; g.grp_out = M; g.gate_rows = M; g.gate_ld = N; g.a_grp_in = M; g.a_grp_out = M;
+    identity_row_maps(g, M, N);
     g.ksplit = ksplit; g.k_valid = Kred;
-    const long long need = (long long)ksplit * M * N * (long long)sizeof(float);
-    if (workspace) {
-        VS_CHECK(workspace_bytes >= need, "vs_gemm_wgrad_tn: workspace of %lld bytes given, %lld needed", (long long)workspace_bytes, need);
-        VS_CHECK(((uintptr_t)workspace & 15) == 0, "vs_gemm_wgrad_tn: workspace must be 16-byte aligned");
-        g.partials = (float *)workspace;
-    }
+    if (attach_workspace("vs_gemm_wgrad_tn", g, workspace, workspace_bytes, (long long)ksplit * M * N * (long long)sizeof(float))) return -1;
     const long long nwg = (long long)vs::cdiv(M, 256) * vs::cdiv(N, 256) * ksplit;
     VS_CHECK(nwg <= 0x7fffffffLL, "vs_gemm_wgrad_tn: grid too large");
     if (dtype == 2) hipLaunchKernelGGL((gemm256_tn_splitk_kernel<true>), dim3((unsigned)nwg), dim3(512), 0, stream, g);
     else hipLaunchKernelGGL((gemm256_tn_splitk_kernel<false>), dim3((unsigned)nwg), dim3(512), 0, stream, g);
-    if (workspace) {
-        const bool v4 = N % 4 == 0 && ldo % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-        const long long items = (long long)M * (v4 ? N / 4 : N);
-        const dim3 grid((unsigned)((items + 255) / 256));
-        if (v4) hipLaunchKernelGGL(splitk_reduce_kernel<4>, grid, dim3(256), 0, stream, (const float *)workspace, out, M, N, 1, ksplit, (long long)ldo, 0LL, accumulate);
-        else hipLaunchKernelGGL(splitk_reduce_kernel<1>, grid, dim3(256), 0, stream, (const float *)workspace, out, M, N, 1, ksplit, (long long)ldo, 0LL, accumulate);
-    }
+    if (workspace) launch_splitk_reduce((const float *)workspace, out, M, N, 1, ksplit, ldo, 0, accumulate, stream);
     VS_HIP(hipGetLastError());
     return 0;
 }
+
+namespace {
+// Second stage of a workspace launch: sums the ks partial tiles of ws into out[t][M, N] (row stride ldo), four columns per thread where
+// every row of every tap is 16-byte aligned; transposed: into out [N, M] (splitk_reduce_t_kernel; one tap, M and N multiples of 32).
+// It stands here, behind the first entry point that used to launch them itself, because the compiler emits the two splitk_reduce_kernel
+// instantiations where the first non-template function names them: moved, the kernels of this file change places in the code object.
+void launch_splitk_reduce(const float *ws, float *out, int M, int N, int ntaps, int ks, long long ldo, long long tap_out_stride, int accumulate,
+                          hipStream_t stream, bool transposed) {
+    if (transposed) {
+        hipLaunchKernelGGL(splitk_reduce_t_kernel, dim3((unsigned)((M / 32) * (N / 32))), dim3(256), 0, stream, ws, out, M, N, ks, ldo, accumulate);
+        return;
+    }
+    const bool v4 = N % 4 == 0 && ldo % 4 == 0 && tap_out_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    const long long items = (long long)ntaps * M * (v4 ? N / 4 : N);
+    const dim3 grid((unsigned)((items + 255) / 256));
+    if (v4) hipLaunchKernelGGL(splitk_reduce_kernel<4>, grid, dim3(256), 0, stream, ws, out, M, N, ntaps, ks, ldo, tap_out_stride, accumulate);
+    else hipLaunchKernelGGL(splitk_reduce_kernel<1>, grid, dim3(256), 0, stream, ws, out, M, N, ntaps, ks, ldo, tap_out_stride, accumulate);
+}
+}  // namespace
 
 // Split-class weight gradient with dY read as it is in memory: out32[M, N] (+)= sum_{k < Kred} A[k, m] Wp[n, k]; A [Kred, M] f32 (row stride lda
 // floats), Wp [N, Kpad] the packed (hi, lo) transposed X of vs_transpose_pack_split (row stride ldw 4-byte units, zero beyond Kred).  M, N multiples
@@ -1134,27 +1154,13 @@ extern "C" int vs_gemm_wgrad_split_atn(const float *A, const void *Wp, float *ou
     GemmArgs g;
     g.A = A; g.W = Wp; g.out = out;
     g.M = M; g.N = N; g.K = Kpad; g.lda = lda; g.ldw = 2 * ldw; g.ldo = ldo;
-    g.grp_in = M; g.grp_out = M; g.gate_rows = M; g.gate_ld = N; g.a_grp_in = M; g.a_grp_out = M;
+    identity_row_maps(g, M, N);
     g.ksplit = ksplit; g.k_valid = Kred;
-    const long long need = (long long)ksplit * M * N * (long long)sizeof(float);
-    if (workspace) {
-        VS_CHECK(workspace_bytes >= need, "vs_gemm_wgrad_split_atn: workspace of %lld bytes given, %lld needed", (long long)workspace_bytes, need);
-        VS_CHECK(((uintptr_t)workspace & 15) == 0, "vs_gemm_wgrad_split_atn: workspace must be 16-byte aligned");
-        g.partials = (float *)workspace;
-    }
+    if (attach_workspace("vs_gemm_wgrad_split_atn", g, workspace, workspace_bytes, (long long)ksplit * M * N * (long long)sizeof(float))) return -1;
     const long long nwg = (long long)(M / 256) * (N / 256) * ksplit;
     VS_CHECK(nwg <= 0x7fffffffLL, "vs_gemm_wgrad_split_atn: grid too large");
     hipLaunchKernelGGL(gemm256_split_atn_splitk_kernel, dim3((unsigned)nwg), dim3(512), 0, stream, g);
-    if (transpose_out) {
-        hipLaunchKernelGGL(splitk_reduce_t_kernel, dim3((unsigned)((M / 32) * (N / 32))), dim3(256), 0, stream, (const float *)workspace, out, M, N, ksplit,
-                           (long long)ldo, accumulate);
-    } else if (workspace) {
-        const bool v4 = ldo % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-        const long long items = (long long)M * (v4 ? N / 4 : N);
-        const dim3 grid((unsigned)((items + 255) / 256));
-        if (v4) hipLaunchKernelGGL(splitk_reduce_kernel<4>, grid, dim3(256), 0, stream, (const float *)workspace, out, M, N, 1, ksplit, (long long)ldo, 0LL, accumulate);
-        else hipLaunchKernelGGL(splitk_reduce_kernel<1>, grid, dim3(256), 0, stream, (const float *)workspace, out, M, N, 1, ksplit, (long long)ldo, 0LL, accumulate);
-    }
+    if (workspace) launch_splitk_reduce((const float *)workspace, out, M, N, 1, ksplit, ldo, 0, accumulate, stream, transpose_out != 0);
     VS_HIP(hipGetLastError());
     return 0;
 }
@@ -1176,26 +1182,15 @@ extern "C" int vs_conv3x3_wgrad_split_atn(const float *x, const void *dyTp, floa
     GemmArgs g;
     g.A = x; g.W = dyTp; g.out = out;
     g.M = Cin; g.N = Cout; g.K = Ppad; g.lda = Cin; g.ldw = 2 * ldw; g.ldo = Cout;
-    g.grp_in = Cin; g.grp_out = Cin; g.gate_rows = Cin; g.gate_ld = Cout; g.a_grp_in = Cin; g.a_grp_out = Cin;
+    identity_row_maps(g, Cin, Cout);
     g.tap_on_a = 1; g.ntaps = 9; g.tap_out_stride = (long long)Cin * Cout;
     g.ksplit = ksplit; g.k_valid = (int)P; g.conv_H = H; g.conv_W = W;
-    const long long need = (long long)ksplit * 9 * Cin * Cout * (long long)sizeof(float);
-    if (workspace) {
-        VS_CHECK(workspace_bytes >= need, "vs_conv3x3_wgrad_split_atn: workspace of %lld bytes given, %lld needed", (long long)workspace_bytes, need);
-        VS_CHECK(((uintptr_t)workspace & 15) == 0, "vs_conv3x3_wgrad_split_atn: workspace must be 16-byte aligned");
-        g.partials = (float *)workspace;
-    }
+    if (attach_workspace("vs_conv3x3_wgrad_split_atn", g, workspace, workspace_bytes, (long long)ksplit * 9 * Cin * Cout * (long long)sizeof(float))) return -1;
     const long long nwg = (long long)(Cin / 256) * (Cout / 256) * 9 * ksplit;
     VS_CHECK(nwg <= 0x7fffffffLL, "vs_conv3x3_wgrad_split_atn: grid too large");
     if (relu_in) hipLaunchKernelGGL(conv3x3_wgrad_split_atn_kernel<true>, dim3((unsigned)nwg), dim3(512), 0, stream, g);
     else hipLaunchKernelGGL(conv3x3_wgrad_split_atn_kernel<false>, dim3((unsigned)nwg), dim3(512), 0, stream, g);
-    if (workspace) {
-        const bool v4 = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-        const long long items = 9LL * Cin * (v4 ? Cout / 4 : Cout);
-        const dim3 grid((unsigned)((items + 255) / 256));
-        if (v4) hipLaunchKernelGGL(splitk_reduce_kernel<4>, grid, dim3(256), 0, stream, (const float *)workspace, out, Cin, Cout, 9, ksplit, (long long)Cout, g.tap_out_stride, accumulate);
-        else hipLaunchKernelGGL(splitk_reduce_kernel<1>, grid, dim3(256), 0, stream, (const float *)workspace, out, Cin, Cout, 9, ksplit, (long long)Cout, g.tap_out_stride, accumulate);
-    }
+    if (workspace) launch_splitk_reduce((const float *)workspace, out, Cin, Cout, 9, ksplit, Cout, g.tap_out_stride, accumulate, stream);
     VS_HIP(hipGetLastError());
     return 0;
 }
@@ -1223,15 +1218,10 @@ extern "C" int vs_conv3x3_wgrad_tn(const void *x, const void *dy, float *out, in
     GemmArgs g;
     g.A = x; g.W = dy; g.out = out;
     g.M = Cin; g.N = Cout; g.K = (int)Kpad; g.lda = Cin; g.ldw = Cout; g.ldo = Cout;
-    g.grp_in = Cin; g.grp_out = Cin; g.gate_rows = Cin; g.gate_ld = Cout; g.a_grp_in = Cin; g.a_grp_out = Cin;
+    identity_row_maps(g, Cin, Cout);
     g.ntaps = 9; g.tap_out_stride = (long long)Cin * Cout;
     g.ksplit = ksplit; g.k_valid = (int)P; g.conv_H = H; g.conv_W = W;
-    const long long need = (long long)ksplit * 9 * Cin * Cout * (long long)sizeof(float);
-    if (workspace) {
-        VS_CHECK(workspace_bytes >= need, "vs_conv3x3_wgrad_tn: workspace of %lld bytes given, %lld needed", (long long)workspace_bytes, need);
-        VS_CHECK(((uintptr_t)workspace & 15) == 0, "vs_conv3x3_wgrad_tn: workspace must be 16-byte aligned");
-        g.partials = (float *)workspace;
-    }
+    if (attach_workspace("vs_conv3x3_wgrad_tn", g, workspace, workspace_bytes, (long long)ksplit * 9 * Cin * Cout * (long long)sizeof(float))) return -1;
     const int G = (Cin <= 128 && 256 % Cin == 0) ? 256 / Cin : 1;   // taps that share one 256-row tile (conv3x3_wgrad_tn_kernel)
     const long long nwg = (long long)(G > 1 ? 1 : vs::cdiv(Cin, 256)) * vs::cdiv(Cout, 256) * vs::cdiv(9, G) * ksplit;
     VS_CHECK(nwg <= 0x7fffffffLL, "vs_conv3x3_wgrad_tn: grid too large");
@@ -1243,13 +1233,7 @@ extern "C" int vs_conv3x3_wgrad_tn(const void *x, const void *dy, float *out, in
         if (relu_in) hipLaunchKernelGGL((conv3x3_wgrad_tn_kernel<false, true>), grid, block, 0, stream, g);
         else hipLaunchKernelGGL((conv3x3_wgrad_tn_kernel<false, false>), grid, block, 0, stream, g);
     }
-    if (workspace) {
-        const bool v4 = Cout % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-        const long long items = 9LL * Cin * (v4 ? Cout / 4 : Cout);
-        const dim3 rg((unsigned)((items + 255) / 256));
-        if (v4) hipLaunchKernelGGL(splitk_reduce_kernel<4>, rg, dim3(256), 0, stream, (const float *)workspace, out, Cin, Cout, 9, ksplit, (long long)Cout, (long long)Cin * Cout, accumulate);
-        else hipLaunchKernelGGL(splitk_reduce_kernel<1>, rg, dim3(256), 0, stream, (const float *)workspace, out, Cin, Cout, 9, ksplit, (long long)Cout, (long long)Cin * Cout, accumulate);
-    }
+    if (workspace) launch_splitk_reduce((const float *)workspace, out, Cin, Cout, 9, ksplit, Cout, g.tap_out_stride, accumulate, stream);
     VS_HIP(hipGetLastError());
     return 0;
 }

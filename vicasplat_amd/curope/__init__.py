@@ -31,10 +31,7 @@ def rope_2d(tokens: torch.Tensor, positions: torch.Tensor, base: float, fwd: flo
         raise RuntimeError(f"unsupported dtype {tokens.dtype}")
     dev = L.require_device(tokens, positions)
     pos = positions.to(torch.int64).contiguous()
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_rope2d(L.ptr(tokens), L.ptr(pos), B, N, H, D, tokens.stride(0), tokens.stride(1), float(base),
-                               float(fwd), _DT[tokens.dtype], L.stream_ptr(dev))
-    L.check(rc, "vs_rope2d")
+    L.call("vs_rope2d", dev, L.ptr(tokens), L.ptr(pos), B, N, H, D, tokens.stride(0), tokens.stride(1), float(base), float(fwd), _DT[tokens.dtype])
 
 
 class _RoPE2DFn(torch.autograd.Function):

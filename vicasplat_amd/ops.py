@@ -5,6 +5,8 @@ Every function requires HIP device tensors and raises otherwise -- there is no P
 """
 from __future__ import annotations
 
+import ctypes
+import math
 from typing import Optional
 
 import torch
@@ -68,10 +70,7 @@ class _RangeGuard:
             return
         self.names.append(f"#{slot} {what} [{rows} x {cols}]{' packed' if packed else ''}")
         dev = d.device
-        with torch.cuda.device(dev):
-            rc = L.lib().vs_range_check(L.ptr(d), rows, cols, d.stride(0), 1 if packed else 0, self.LIMIT, L.ptr(self.flags), slot,
-                                        L.stream_ptr(dev))
-        L.check(rc, "vs_range_check")
+        L.call("vs_range_check", dev, L.ptr(d), rows, cols, d.stride(0), 1 if packed else 0, self.LIMIT, L.ptr(self.flags), slot)
 
     def report(self) -> list:
         """[(call, flags)] of the calls whose operand left the f16 range (1 = finite |x| >= 65520, 2 = non-finite f32 input, 4 = a packed hi
@@ -145,7 +144,6 @@ def split_scale_exp(w: torch.Tensor, with_nonzero: bool = False):
     """Power-of-two exponent e with max|w| 2^e in [2^13, 2^14) (one host read of the maximum); 0 for an all-zero / non-finite weight.
     with_nonzero: also return whether the exponent came from an actual finite non-zero maximum (a cache must not keep the 0 of a
     zero-initialised layer: it would pack the layer unscaled long after its weights have moved)."""
-    import math
     amax = float(w.detach().abs().max())
     ok = amax != 0.0 and math.isfinite(amax)
     e = max(-24, min(24, 13 - math.frexp(amax)[1] + 1)) if ok else 0
@@ -162,9 +160,7 @@ def split_pack_weight(w: torch.Tensor, scale_exp: Optional[int] = None) -> Split
     # scale_exp given: no host synchronisation (callers that pack every step cache the exponent; 0 = unscaled, the activations' convention)
     e = split_scale_exp(w2) if scale_exp is None else int(scale_exp)
     out = torch.empty((N, K), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_split_pack_weight(L.ptr(w2), w2.stride(0), L.ptr(out), out.stride(0), N, K, e, L.stream_ptr(dev))
-    L.check(rc, "vs_split_pack_weight")
+    L.call("vs_split_pack_weight", dev, L.ptr(w2), w2.stride(0), L.ptr(out), out.stride(0), N, K, e)
     return SplitWeight(out.view(w.shape[0], *w.shape[1:]) if w.dim() > 2 else out, 2.0 ** (-e), w.shape)
 
 
@@ -186,11 +182,8 @@ def layernorm_mod(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, out
         mod_ld = scale.stride(0)
     elif shift is not None:
         mod_ld = shift.stride(0)
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_layernorm_mod(L.ptr(x), x.stride(0), L.ptr(weight), L.ptr(bias), L.ptr(scale), L.ptr(shift),
-                                      mod_rows, mod_ld, L.ptr(out), out.stride(-2), _DT[out.dtype] if odt is None else odt, M, C, eps, grp_in,
-                                      grp_out, grp_off, L.stream_ptr(dev))
-    L.check(rc, "vs_layernorm_mod")
+    L.call("vs_layernorm_mod", dev, L.ptr(x), x.stride(0), L.ptr(weight), L.ptr(bias), L.ptr(scale), L.ptr(shift), mod_rows, mod_ld, L.ptr(out),
+           out.stride(-2), _DT[out.dtype] if odt is None else odt, M, C, eps, grp_in, grp_out, grp_off)
     return out_obj
 
 
@@ -205,10 +198,8 @@ def linear_f32(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], r
         wf = wf.contiguous()
     bf = None if bias is None else bias.detach().float().contiguous()
     out = torch.empty((x2.shape[0], wf.shape[0]), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_linear_f32(L.ptr(x2), x2.stride(0), L.ptr(wf), wf.stride(0), L.ptr(bf), L.ptr(out), out.stride(0), x2.shape[0], wf.shape[0],
-                                   x2.shape[1], int(relu_in), L.stream_ptr(dev))
-    L.check(rc, "vs_linear_f32")
+    L.call("vs_linear_f32", dev, L.ptr(x2), x2.stride(0), L.ptr(wf), wf.stride(0), L.ptr(bf), L.ptr(out), out.stride(0), x2.shape[0], wf.shape[0],
+           x2.shape[1], int(relu_in))
     return out.view(*x.shape[:-1], wf.shape[0])
 
 
@@ -217,9 +208,7 @@ def silu_cast(x: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     dev = L.require_device(x)
     assert x.dtype == torch.float32 and x.is_contiguous() and x.numel() % 4 == 0
     out = torch.empty(x.shape, dtype=dtype, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_silu_cast(L.ptr(x), L.ptr(out), x.numel(), _DT[dtype], L.stream_ptr(dev))
-    L.check(rc, "vs_silu_cast")
+    L.call("vs_silu_cast", dev, L.ptr(x), L.ptr(out), x.numel(), _DT[dtype])
     return out
 
 
@@ -242,11 +231,8 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], out: to
     else:
         assert out.dtype == torch.float32
     gate_ld = gate.stride(0) if gate is not None else 0
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_gemm_bias_act(L.ptr(a), L.ptr(w), L.ptr(bias), L.ptr(out), L.ptr(gate), M, N, K, a.stride(0),
-                                      w.stride(0), out.stride(-2), epilogue, _DTX[a.dtype], grp_in, grp_out, grp_off,
-                                      gate_rows, gate_ld, a_grp_in, a_grp_out, a_grp_off, L.stream_ptr(dev))
-    L.check(rc, "vs_gemm_bias_act")
+    L.call("vs_gemm_bias_act", dev, L.ptr(a), L.ptr(w), L.ptr(bias), L.ptr(out), L.ptr(gate), M, N, K, a.stride(0), w.stride(0), out.stride(-2),
+           epilogue, _DTX[a.dtype], grp_in, grp_out, grp_off, gate_rows, gate_ld, a_grp_in, a_grp_out, a_grp_off)
     return out
 
 
@@ -268,13 +254,9 @@ def _gemm_split(a, w: SplitWeight, bias, out, epilogue, *, gate=None, gate_rows=
     M = a.shape[0] if M is None else M
     if RANGE_GUARD.enabled:
         RANGE_GUARD.check(f"gemm A x W[{wd.shape[0]}] epi {epilogue}", SplitWeight(a, 1.0, a.shape) if packed else a)
-    fn = L.lib().vs_gemm_split_packed if packed else L.lib().vs_gemm_split
-    with torch.cuda.device(dev):
-        rc = fn(L.ptr(a), L.ptr(wd), w.acc_scale, L.ptr(bias), L.ptr(out), L.ptr(gate), L.ptr(resid), M, wd.shape[0], a.shape[1],
-                                   a.stride(0), wd.stride(0), out.stride(-2), epilogue, grp_in, grp_out, grp_off, gate_rows,
-                                   gate.stride(0) if gate is not None else 0, a_grp_in, a_grp_out, a_grp_off, L.ptr(pos), L.ptr(kind), C,
-                                   base2d, theta1d, L.stream_ptr(dev))
-    L.check(rc, "vs_gemm_split")
+    L.call("vs_gemm_split_packed" if packed else "vs_gemm_split", dev, L.ptr(a), L.ptr(wd), w.acc_scale, L.ptr(bias), L.ptr(out), L.ptr(gate),
+           L.ptr(resid), M, wd.shape[0], a.shape[1], a.stride(0), wd.stride(0), out.stride(-2), epilogue, grp_in, grp_out, grp_off, gate_rows,
+           gate.stride(0) if gate is not None else 0, a_grp_in, a_grp_out, a_grp_off, L.ptr(pos), L.ptr(kind), C, base2d, theta1d)
     return out_obj
 
 
@@ -289,11 +271,8 @@ def gemm_resid(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], r
     assert a.dtype == w.dtype and a.dtype in _OPERAND_DTYPES and a.stride(1) == 1 and w.stride(1) == 1
     assert resid.dtype == torch.float32 and resid.is_contiguous() and resid.shape == (a.shape[0], w.shape[0])
     out = torch.empty_like(resid)
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_gemm_resid(L.ptr(a), L.ptr(w), L.ptr(bias), L.ptr(resid), L.ptr(out), L.ptr(gate), a.shape[0], w.shape[0], a.shape[1],
-                                   a.stride(0), w.stride(0), out.stride(0), _DTX[a.dtype], gate_rows, gate.stride(0) if gate is not None else 0,
-                                   L.stream_ptr(dev))
-    L.check(rc, "vs_gemm_resid")
+    L.call("vs_gemm_resid", dev, L.ptr(a), L.ptr(w), L.ptr(bias), L.ptr(resid), L.ptr(out), L.ptr(gate), a.shape[0], w.shape[0], a.shape[1],
+           a.stride(0), w.stride(0), out.stride(0), _DTX[a.dtype], gate_rows, gate.stride(0) if gate is not None else 0)
     return out
 
 
@@ -311,11 +290,8 @@ def gemm_qkv_rope(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]
     assert a.dim() == 2 and w.dim() == 2 and a.stride(1) == 1 and w.stride(1) == 1 and a.shape[1] == w.shape[1]
     assert pos.dtype == torch.int32 and pos.is_contiguous() and (kind is None or (kind.dtype == torch.uint8 and kind.is_contiguous()))
     M = a.shape[0] if M is None else M
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_gemm_qkv_rope(L.ptr(a), L.ptr(w), L.ptr(bias), L.ptr(out), M, w.shape[0], a.shape[1], a.stride(0), w.stride(0),
-                                      out.stride(-2), _DTX[a.dtype], grp_in, grp_out, grp_off, a_grp_in, a_grp_out, a_grp_off,
-                                      L.ptr(pos), L.ptr(kind), C, base2d, theta1d, L.stream_ptr(dev))
-    L.check(rc, "vs_gemm_qkv_rope")
+    L.call("vs_gemm_qkv_rope", dev, L.ptr(a), L.ptr(w), L.ptr(bias), L.ptr(out), M, w.shape[0], a.shape[1], a.stride(0), w.stride(0), out.stride(-2),
+           _DTX[a.dtype], grp_in, grp_out, grp_off, a_grp_in, a_grp_out, a_grp_off, L.ptr(pos), L.ptr(kind), C, base2d, theta1d)
     return out
 
 
@@ -326,10 +302,8 @@ def rope_qk(buf: torch.Tensor, H: int, k_col: int, pos: torch.Tensor, kind: Opti
     dev = L.require_device(buf, pos, kind)
     assert buf.dim() == 2 and buf.stride(1) == 1 and pos.dtype == torch.int32 and pos.is_contiguous()
     assert kind is None or (kind.dtype == torch.uint8 and kind.is_contiguous())
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_rope_qk_dir(L.ptr(buf), buf.stride(0), buf.shape[0], H, k_col, L.ptr(pos), L.ptr(kind), base2d, theta1d,
-                                    -1.0 if inverse else 1.0, _DT[buf.dtype], L.stream_ptr(dev))
-    L.check(rc, "vs_rope_qk")
+    L.call("vs_rope_qk_dir", dev, L.ptr(buf), buf.stride(0), buf.shape[0], H, k_col, L.ptr(pos), L.ptr(kind), base2d, theta1d,
+           -1.0 if inverse else 1.0, _DT[buf.dtype])
     return buf
 
 
@@ -359,12 +333,9 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tens
     if split and RANGE_GUARD.enabled:
         for nm_, t_ in (("q", q), ("k", k), ("v", v)):
             RANGE_GUARD.check(f"attention {nm_} (H {H}, Lq {Lq})", SplitWeight(t_, 1.0, t_.shape) if in_packed else t_, cols=H * 64)
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_attention_lse(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), nbatch, H, Lq, Lk, q_batch_rows, k_batch_rows,
-                                      q.stride(0), k.stride(0), v.stride(0), out.stride(0), L.ptr(kv_seg), L.ptr(q_kvlen), scale,
-                                      (4 + (16 if out_packed else 0) + (32 if in_packed else 0)) if split else _DTX[q.dtype], L.ptr(lse),
-                                      L.stream_ptr(dev))
-    L.check(rc, "vs_attention")
+    L.call("vs_attention_lse", dev, L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), nbatch, H, Lq, Lk, q_batch_rows, k_batch_rows, q.stride(0), k.stride(0),
+           v.stride(0), out.stride(0), L.ptr(kv_seg), L.ptr(q_kvlen), scale,
+           (4 + (16 if out_packed else 0) + (32 if in_packed else 0)) if split else _DTX[q.dtype], L.ptr(lse))
     return out_obj
 
 
@@ -391,22 +362,15 @@ def attention_backward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: t
         assert kv_seg is None and dv_out is not None, "direct dk / dv need key rows with a single owner (no key segments)"
         for t, ref in ((dk_out, k), (dv_out, v)):
             assert t.shape == (ref.shape[0], Cc) and t.dtype == q.dtype and t.stride(1) == 1
-        with torch.cuda.device(dev):
-            rc = L.lib().vs_attention_backward16(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), L.ptr(dout), L.ptr(lse), L.ptr(delta), L.ptr(dq),
-                                                 L.ptr(dk_out), L.ptr(dv_out), nbatch, H, Lq, Lk, q_batch_rows, k_batch_rows, q.stride(0),
-                                                 k.stride(0), v.stride(0), out.stride(0), dout.stride(0), dq.stride(0), dk_out.stride(0),
-                                                 dv_out.stride(0), L.ptr(q_kvlen), scale, _DT[q.dtype], L.stream_ptr(dev))
-        L.check(rc, "vs_attention_backward16")
+        L.call("vs_attention_backward16", dev, L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), L.ptr(dout), L.ptr(lse), L.ptr(delta), L.ptr(dq),
+               L.ptr(dk_out), L.ptr(dv_out), nbatch, H, Lq, Lk, q_batch_rows, k_batch_rows, q.stride(0), k.stride(0), v.stride(0), out.stride(0),
+               dout.stride(0), dq.stride(0), dk_out.stride(0), dv_out.stride(0), L.ptr(q_kvlen), scale, _DT[q.dtype])
         return dq, dk_out, dv_out
     dk = torch.zeros((k.shape[0], Cc), dtype=torch.float32, device=dev)
     dv = torch.zeros((v.shape[0], Cc), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_attention_backward(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), L.ptr(dout), L.ptr(lse), L.ptr(delta), L.ptr(dq),
-                                           L.ptr(dk), L.ptr(dv), nbatch, H, Lq, Lk, q_batch_rows, k_batch_rows, q.stride(0),
-                                           k.stride(0), v.stride(0), out.stride(0), dout.stride(0), dq.stride(0), dk.stride(0),
-                                           dv.stride(0), L.ptr(kv_seg), L.ptr(q_kvlen), max_keys, scale, _DT[q.dtype],
-                                           L.stream_ptr(dev))
-    L.check(rc, "vs_attention_backward")
+    L.call("vs_attention_backward", dev, L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), L.ptr(dout), L.ptr(lse), L.ptr(delta), L.ptr(dq), L.ptr(dk),
+           L.ptr(dv), nbatch, H, Lq, Lk, q_batch_rows, k_batch_rows, q.stride(0), k.stride(0), v.stride(0), out.stride(0), dout.stride(0),
+           dq.stride(0), dk.stride(0), dv.stride(0), L.ptr(kv_seg), L.ptr(q_kvlen), max_keys, scale, _DT[q.dtype])
     return dq, dk, dv
 
 
@@ -431,13 +395,9 @@ def gaussian_adapter(pts: torch.Tensor, gs: torch.Tensor, sh_mask: torch.Tensor,
                scales=torch.empty(N, H, W, 3, **f), rotations=torch.empty(N, H, W, 4, **f),
                raw=torch.empty(N, H, W, 11 + 3 * d_sh, **f) if want_raw else None)
     act = {"bounded": 0, "exp": 1, "softplus": 2}[scale_act]
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_gaussian_adapter(L.ptr(pts), pts.stride(3), pts.stride(1), L.ptr(gs), gs.stride(3), gs.stride(1),
-                                         _DT[pts.dtype], npix, d_sh, L.ptr(sh_mask), act, scale_min, scale_max,
-                                         opacity_exponent, L.ptr(out["means"]), L.ptr(out["covariances"]), L.ptr(out["harmonics"]),
-                                         L.ptr(out["opacities"]), L.ptr(out["scales"]), L.ptr(out["rotations"]), L.ptr(out["raw"]),
-                                         L.stream_ptr(dev))
-    L.check(rc, "vs_gaussian_adapter")
+    L.call("vs_gaussian_adapter", dev, L.ptr(pts), pts.stride(3), pts.stride(1), L.ptr(gs), gs.stride(3), gs.stride(1), _DT[pts.dtype], npix, d_sh,
+           L.ptr(sh_mask), act, scale_min, scale_max, opacity_exponent, L.ptr(out["means"]), L.ptr(out["covariances"]), L.ptr(out["harmonics"]),
+           L.ptr(out["opacities"]), L.ptr(out["scales"]), L.ptr(out["rotations"]), L.ptr(out["raw"]))
     return out
 
 
@@ -460,11 +420,8 @@ def gaussian_adapter_backward(pts: torch.Tensor, gs: torch.Tensor, sh_mask: torc
     d_pts = torch.empty(pts.shape[:-1] + (pl,), dtype=pts.dtype, device=dev)
     d_gs = torch.empty(gs.shape[:-1] + (gl,), dtype=gs.dtype, device=dev)
     act = {"bounded": 0, "exp": 1, "softplus": 2}[scale_act]
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_gaussian_adapter_backward(L.ptr(pts), pts.shape[-1], L.ptr(gs), _DT[pts.dtype], npix, d_sh, L.ptr(sh_mask), act,
-                                                  scale_min, scale_max, opacity_exponent, L.ptr(d_means), L.ptr(d_cov), L.ptr(d_harm),
-                                                  L.ptr(d_op), L.ptr(d_raw), L.ptr(d_pts), pl, L.ptr(d_gs), gl, L.stream_ptr(dev))
-    L.check(rc, "vs_gaussian_adapter_backward")
+    L.call("vs_gaussian_adapter_backward", dev, L.ptr(pts), pts.shape[-1], L.ptr(gs), _DT[pts.dtype], npix, d_sh, L.ptr(sh_mask), act, scale_min,
+           scale_max, opacity_exponent, L.ptr(d_means), L.ptr(d_cov), L.ptr(d_harm), L.ptr(d_op), L.ptr(d_raw), L.ptr(d_pts), pl, L.ptr(d_gs), gl)
     return d_pts[..., :pts.shape[-1]], d_gs[..., :gs.shape[-1]]
 
 
@@ -496,21 +453,15 @@ def conv3x3_nhwc(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] 
         RANGE_GUARD.check(f"conv3x3 {Cin}->{Cout} @{H}x{W}", SplitWeight(x.view(-1, Cin), 1.0, (N * H * W, Cin)) if xin_packed else x)
     if split and residual2 is not None:      # split class: out = conv + bias + residual + residual2 in the epilogue (no add pass)
         L.require_device(residual2)
-        with torch.cuda.device(dev):
-            rc = L.lib().vs_conv3x3_split_res2_nhwc(L.ptr(x), L.ptr(w.data), w.acc_scale, L.ptr(bias), L.ptr(residual), L.ptr(residual2), L.ptr(out), N, H, W,
-                                                    Cin, Cout, stride, int(relu_in), int(relu_out), L.stream_ptr(dev))
-        L.check(rc, "vs_conv3x3_split_res2_nhwc")
+        L.call("vs_conv3x3_split_res2_nhwc", dev, L.ptr(x), L.ptr(w.data), w.acc_scale, L.ptr(bias), L.ptr(residual), L.ptr(residual2), L.ptr(out), N,
+               H, W, Cin, Cout, stride, int(relu_in), int(relu_out))
         return out
     if split:
-        with torch.cuda.device(dev):
-            rc = L.lib().vs_conv3x3_split_nhwc(L.ptr(x), L.ptr(w.data), w.acc_scale, L.ptr(bias), L.ptr(residual), L.ptr(out), N, H, W, Cin, Cout,
-                                               stride, int(relu_in) | (16 if xin_packed else 0), int(relu_out), L.stream_ptr(dev))
-        L.check(rc, "vs_conv3x3_split_nhwc")
+        L.call("vs_conv3x3_split_nhwc", dev, L.ptr(x), L.ptr(w.data), w.acc_scale, L.ptr(bias), L.ptr(residual), L.ptr(out), N, H, W, Cin, Cout,
+               stride, int(relu_in) | (16 if xin_packed else 0), int(relu_out))
         return out
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_conv3x3_nhwc(L.ptr(x), L.ptr(w), L.ptr(bias), L.ptr(residual), L.ptr(out), N, H, W, Cin, Cout, stride,
-                                     int(relu_in), int(relu_out), _DTX[x.dtype], L.stream_ptr(dev))
-    L.check(rc, "vs_conv3x3_nhwc")
+    L.call("vs_conv3x3_nhwc", dev, L.ptr(x), L.ptr(w), L.ptr(bias), L.ptr(residual), L.ptr(out), N, H, W, Cin, Cout, stride, int(relu_in),
+           int(relu_out), _DTX[x.dtype])
     return out
 
 
@@ -531,10 +482,8 @@ def conv3x3_head1x1_nhwc(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.
         out = torch.empty((N, H, W, c2pad), dtype=torch.float32, device=dev)
         if RANGE_GUARD.enabled:
             RANGE_GUARD.check(f"fused head conv3x3 {Cin}->256 -> 1x1 @{H}x{W}", SplitWeight(x.view(-1, Cin), 1.0, (N * H * W, Cin)) if xin_packed else x)
-        with torch.cuda.device(dev):
-            rc = L.lib().vs_conv3x3_head1x1_split_nhwc(L.ptr(x), L.ptr(w.data), w.acc_scale, L.ptr(bias), L.ptr(w2.data), w2.acc_scale, L.ptr(bias2),
-                                                       L.ptr(out), N, H, W, Cin, n_out, c2pad, c2pad, int(relu_out) | (16 if xin_packed else 0), L.stream_ptr(dev))
-        L.check(rc, "vs_conv3x3_head1x1_split_nhwc")
+        L.call("vs_conv3x3_head1x1_split_nhwc", dev, L.ptr(x), L.ptr(w.data), w.acc_scale, L.ptr(bias), L.ptr(w2.data), w2.acc_scale, L.ptr(bias2),
+               L.ptr(out), N, H, W, Cin, n_out, c2pad, c2pad, int(relu_out) | (16 if xin_packed else 0))
         return out
     if isinstance(w, SplitWeight):   # split operands: the dot-product form (Cout = 128, n_out <= 4), f32 in / out, w2 f32 [>= n_out, 128]
         xin_packed = isinstance(x, SplitWeight)      # the input already packed (upsample2x_nhwc(..., packed=True)): no conversion in the main loop
@@ -547,10 +496,8 @@ def conv3x3_head1x1_nhwc(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.
         out = torch.empty((N, H, W, 4), dtype=torch.float32, device=dev)
         if RANGE_GUARD.enabled:
             RANGE_GUARD.check(f"fused head conv3x3 {Cin}->128 -> dot @{H}x{W}", SplitWeight(x.view(-1, Cin), 1.0, (N * H * W, Cin)) if xin_packed else x)
-        with torch.cuda.device(dev):
-            rc = L.lib().vs_conv3x3_head_dot_split_nhwc(L.ptr(x), L.ptr(w.data), w.acc_scale, L.ptr(bias), L.ptr(w2), L.ptr(bias2), L.ptr(out), N, H, W,
-                                                        Cin, n_out, 4, 0, int(relu_out) | (16 if xin_packed else 0), L.stream_ptr(dev))
-        L.check(rc, "vs_conv3x3_head_dot_split_nhwc")
+        L.call("vs_conv3x3_head_dot_split_nhwc", dev, L.ptr(x), L.ptr(w.data), w.acc_scale, L.ptr(bias), L.ptr(w2), L.ptr(bias2), L.ptr(out), N, H, W,
+               Cin, n_out, 4, 0, int(relu_out) | (16 if xin_packed else 0))
         return out
     dev = L.require_device(x, w, bias, w2, bias2)
     assert x.dim() == 4 and x.is_contiguous() and w.is_contiguous() and w2.is_contiguous() and x.dtype == w.dtype == w2.dtype
@@ -565,10 +512,8 @@ def conv3x3_head1x1_nhwc(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.
         c2pad, ld2 = n_out, 4
         assert w2.shape[0] >= n_out and bias2.numel() >= 4
     out = torch.empty((N, H, W, ld2), dtype=x.dtype, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_conv3x3_head1x1_nhwc(L.ptr(x), L.ptr(w), L.ptr(bias), L.ptr(w2), L.ptr(bias2), L.ptr(out), N, H, W, Cin, Cout, n_out,
-                                             c2pad, ld2, 0, int(relu_out), _DT[x.dtype], L.stream_ptr(dev))
-    L.check(rc, "vs_conv3x3_head1x1_nhwc")
+    L.call("vs_conv3x3_head1x1_nhwc", dev, L.ptr(x), L.ptr(w), L.ptr(bias), L.ptr(w2), L.ptr(bias2), L.ptr(out), N, H, W, Cin, Cout, n_out, c2pad,
+           ld2, 0, int(relu_out), _DT[x.dtype])
     return out
 
 
@@ -623,16 +568,11 @@ def conv7x7_rgb_nhwc(img_padded: torch.Tensor, w: torch.Tensor, bias: Optional[t
             if RANGE_GUARD.enabled:
                 RANGE_GUARD.check(f"stem + upsample-add: trunk {Cout} @{H // 2}x{W // 2}", up_add)
             outp = torch.empty((N, H, W, Cout), dtype=torch.int32, device=dev)
-            with torch.cuda.device(dev):
-                rc = L.lib().vs_conv7x7_rgb_split_up_nhwc(L.ptr(img_padded), L.ptr(w.data), w.acc_scale, L.ptr(bias), L.ptr(up_add), L.ptr(outp), N, H, W,
-                                                          Hp, Wp, Cout, L.stream_ptr(dev))
-            L.check(rc, "vs_conv7x7_rgb_split_up_nhwc")
+            L.call("vs_conv7x7_rgb_split_up_nhwc", dev, L.ptr(img_padded), L.ptr(w.data), w.acc_scale, L.ptr(bias), L.ptr(up_add), L.ptr(outp), N, H,
+                   W, Hp, Wp, Cout)
             return SplitWeight(outp, 1.0, outp.shape)
         out = torch.empty((N, H, W, Cout), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = L.lib().vs_conv7x7_rgb_split_nhwc(L.ptr(img_padded), L.ptr(w.data), w.acc_scale, L.ptr(bias), L.ptr(out), N, H, W, Hp, Wp, Cout,
-                                                   L.stream_ptr(dev))
-        L.check(rc, "vs_conv7x7_rgb_split_nhwc")
+        L.call("vs_conv7x7_rgb_split_nhwc", dev, L.ptr(img_padded), L.ptr(w.data), w.acc_scale, L.ptr(bias), L.ptr(out), N, H, W, Hp, Wp, Cout)
         return out
     dev = L.require_device(img_padded, w, bias)
     N, Hp, Wp, C = img_padded.shape
@@ -640,10 +580,7 @@ def conv7x7_rgb_nhwc(img_padded: torch.Tensor, w: torch.Tensor, bias: Optional[t
     assert C == 3 and img_padded.is_contiguous() and w.shape == (Cout, 8, 32) and w.is_contiguous() and img_padded.dtype == w.dtype
     assert img_padded.untyped_storage().nbytes() >= (img_padded.storage_offset() + img_padded.numel() + Wp * 3 + 64) * 2
     out = torch.empty((N, H, W, Cout), dtype=w.dtype, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_conv7x7_rgb_nhwc(L.ptr(img_padded), L.ptr(w), L.ptr(bias), L.ptr(out), N, H, W, Hp, Wp, Cout,
-                                         _DT[w.dtype], L.stream_ptr(dev))
-    L.check(rc, "vs_conv7x7_rgb_nhwc")
+    L.call("vs_conv7x7_rgb_nhwc", dev, L.ptr(img_padded), L.ptr(w), L.ptr(bias), L.ptr(out), N, H, W, Hp, Wp, Cout, _DT[w.dtype])
     return out
 
 
@@ -654,9 +591,7 @@ def im2col7x7_rgb(frames: torch.Tensor, dtype: torch.dtype, ld: int = 256) -> to
     N, C, H, W = frames.shape
     assert C == 3 and frames.dtype == torch.float32 and frames.is_contiguous() and ld % 8 == 0 and ld >= 148
     out = torch.empty((N, H * W, ld), dtype=dtype, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_im2col7x7_rgb(L.ptr(frames), L.ptr(out), N, H, W, ld, {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}[dtype], L.stream_ptr(dev))
-    L.check(rc, "vs_im2col7x7_rgb")
+    L.call("vs_im2col7x7_rgb", dev, L.ptr(frames), L.ptr(out), N, H, W, ld, {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}[dtype])
     return out
 
 
@@ -673,10 +608,8 @@ def stem7x7_up_split_stream(img_padded: torch.Tensor, w: torch.Tensor, bias: tor
         RANGE_GUARD.check(f"stem + upsample-add: trunk {Cout} @{H // 2}x{W // 2}", up_add)
     outp = torch.empty((N, H, W, Cout), dtype=torch.int32, device=dev)
     nwg = max(1, min(N * (W // 32), torch.cuda.get_device_properties(dev).multi_processor_count))
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_stem7x7_up_split_stream(L.ptr(img_padded), L.ptr(w), int(scale_exp), L.ptr(bias), L.ptr(up_add), L.ptr(outp), N, H, W, Hp, Wp, Cout,
-                                                nwg, L.stream_ptr(dev))
-    L.check(rc, "vs_stem7x7_up_split_stream")
+    L.call("vs_stem7x7_up_split_stream", dev, L.ptr(img_padded), L.ptr(w), int(scale_exp), L.ptr(bias), L.ptr(up_add), L.ptr(outp), N, H, W, Hp, Wp,
+           Cout, nwg)
     return SplitWeight(outp, 1.0, outp.shape)
 
 
@@ -690,9 +623,7 @@ def upsample2x_nhwc(x: torch.Tensor, add: Optional[torch.Tensor] = None, relu_ad
     assert not packed or (x.dtype == torch.float32 and Cc % 32 == 0 and H >= 2 and W >= 2)
     out = torch.empty((N, 2 * H, 2 * W, Cc), dtype=torch.int32 if packed else x.dtype, device=dev)
     assert add is None or (add.shape == out.shape and add.is_contiguous() and add.dtype == x.dtype)
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_upsample2x_nhwc(L.ptr(x), L.ptr(add), L.ptr(out), N, H, W, Cc, int(relu_add) | (16 if packed else 0), _DTX[x.dtype], L.stream_ptr(dev))
-    L.check(rc, "vs_upsample2x_nhwc")
+    L.call("vs_upsample2x_nhwc", dev, L.ptr(x), L.ptr(add), L.ptr(out), N, H, W, Cc, int(relu_add) | (16 if packed else 0), _DTX[x.dtype])
     return SplitWeight(out, 1.0, out.shape) if packed else out
 
 
@@ -733,10 +664,8 @@ def transpose16(x: torch.Tensor, pad_to: int = 1, *, colsum_out: Optional[torch.
         ld_out, sstride = out.stride(0), 0
     if colsum_out is not None:
         assert colsum_out.dtype == torch.float32 and colsum_out.is_contiguous() and colsum_out.numel() == Cc
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_transpose16_ex(L.ptr(x), x.stride(0), L.ptr(out), ld_out, R, Cc, Rpad, L.ptr(colsum_out), _DT[x.dtype],
-                                       bh, bw, int(relu), slices, halo, sstride, L.stream_ptr(dev))
-    L.check(rc, "vs_transpose16_ex")
+    L.call("vs_transpose16_ex", dev, L.ptr(x), x.stride(0), L.ptr(out), ld_out, R, Cc, Rpad, L.ptr(colsum_out), _DT[x.dtype], bh, bw, int(relu),
+           slices, halo, sstride)
     return out
 
 
@@ -758,9 +687,7 @@ def colsum(x: torch.Tensor) -> torch.Tensor:
     dev = L.require_device(x)
     assert x.dim() == 2 and x.stride(1) == 1
     out = torch.empty(x.shape[1], dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_colsum(L.ptr(x), x.stride(0), L.ptr(out), x.shape[0], x.shape[1], _DT3[x.dtype], L.stream_ptr(dev))
-    L.check(rc, "vs_colsum")
+    L.call("vs_colsum", dev, L.ptr(x), x.stride(0), L.ptr(out), x.shape[0], x.shape[1], _DT3[x.dtype])
     return out
 
 
@@ -774,15 +701,11 @@ def gated_resid(x: torch.Tensor, y: torch.Tensor, gate: Optional[torch.Tensor] =
     if out is None:
         out = torch.empty_like(x)
     if y.dtype == torch.float32:      # f32 branch (split / f32 operand classes)
-        with torch.cuda.device(dev):
-            rc = L.lib().vs_gated_resid_f32(L.ptr(x), L.ptr(y), y.stride(0), L.ptr(gate), gate_rows, L.ptr(out), x.shape[0], x.shape[1], grp_in,
-                                            grp_out, grp_off, L.stream_ptr(dev))
-        L.check(rc, "vs_gated_resid_f32")
+        L.call("vs_gated_resid_f32", dev, L.ptr(x), L.ptr(y), y.stride(0), L.ptr(gate), gate_rows, L.ptr(out), x.shape[0], x.shape[1], grp_in,
+               grp_out, grp_off)
         return out
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_gated_resid(L.ptr(x), L.ptr(y), y.stride(0), L.ptr(gate), gate_rows, L.ptr(out), x.shape[0], x.shape[1], grp_in,
-                                    grp_out, grp_off, _DT[y.dtype], L.stream_ptr(dev))
-    L.check(rc, "vs_gated_resid")
+    L.call("vs_gated_resid", dev, L.ptr(x), L.ptr(y), y.stride(0), L.ptr(gate), gate_rows, L.ptr(out), x.shape[0], x.shape[1], grp_in, grp_out,
+           grp_off, _DT[y.dtype])
     return out
 
 
@@ -794,16 +717,11 @@ def gated_resid_backward(dout: torch.Tensor, y: torch.Tensor, gate: Optional[tor
     assert dout.dim() == 2 and dout.is_contiguous() and dout.dtype == torch.float32 and dy.stride(1) == 1 and dy.dtype == y.dtype
     dgate = None if gate is None else torch.zeros_like(gate)
     if y.dtype == torch.float32:
-        with torch.cuda.device(dev):
-            rc = L.lib().vs_gated_resid_backward_f32(L.ptr(dout), L.ptr(y), y.stride(0), L.ptr(gate), gate_rows, L.ptr(dy), dy.stride(0),
-                                                     L.ptr(dgate), dout.shape[0], dout.shape[1], grp_in, grp_out, grp_off, L.stream_ptr(dev))
-        L.check(rc, "vs_gated_resid_backward_f32")
+        L.call("vs_gated_resid_backward_f32", dev, L.ptr(dout), L.ptr(y), y.stride(0), L.ptr(gate), gate_rows, L.ptr(dy), dy.stride(0), L.ptr(dgate),
+               dout.shape[0], dout.shape[1], grp_in, grp_out, grp_off)
         return dgate
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_gated_resid_backward(L.ptr(dout), L.ptr(y), y.stride(0), L.ptr(gate), gate_rows, L.ptr(dy), dy.stride(0),
-                                             L.ptr(dgate), dout.shape[0], dout.shape[1], grp_in, grp_out, grp_off, _DT[y.dtype],
-                                             L.stream_ptr(dev))
-    L.check(rc, "vs_gated_resid_backward")
+    L.call("vs_gated_resid_backward", dev, L.ptr(dout), L.ptr(y), y.stride(0), L.ptr(gate), gate_rows, L.ptr(dy), dy.stride(0), L.ptr(dgate),
+           dout.shape[0], dout.shape[1], grp_in, grp_out, grp_off, _DT[y.dtype])
     return dgate
 
 
@@ -813,13 +731,9 @@ def gelu16(z: torch.Tensor) -> torch.Tensor:
     assert z.is_contiguous() and z.dtype in (torch.float16, torch.bfloat16, torch.float32)
     out = torch.empty_like(z)
     if z.dtype == torch.float32:
-        with torch.cuda.device(dev):
-            rc = L.lib().vs_gelu_f32(L.ptr(z), L.ptr(out), z.numel(), L.stream_ptr(dev))
-        L.check(rc, "vs_gelu_f32")
+        L.call("vs_gelu_f32", dev, L.ptr(z), L.ptr(out), z.numel())
         return out
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_gelu16(L.ptr(z), L.ptr(out), z.numel(), _DT[z.dtype], L.stream_ptr(dev))
-    L.check(rc, "vs_gelu16")
+    L.call("vs_gelu16", dev, L.ptr(z), L.ptr(out), z.numel(), _DT[z.dtype])
     return out
 
 
@@ -829,13 +743,9 @@ def gelu_backward(dy: torch.Tensor, z: torch.Tensor) -> torch.Tensor:
     assert dy.shape == z.shape and dy.dtype == z.dtype and dy.is_contiguous() and z.is_contiguous()
     dz = torch.empty_like(dy)
     if z.dtype == torch.float32:
-        with torch.cuda.device(dev):
-            rc = L.lib().vs_gelu_backward_f32(L.ptr(dy), L.ptr(z), L.ptr(dz), dy.numel(), L.stream_ptr(dev))
-        L.check(rc, "vs_gelu_backward_f32")
+        L.call("vs_gelu_backward_f32", dev, L.ptr(dy), L.ptr(z), L.ptr(dz), dy.numel())
         return dz
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_gelu_backward(L.ptr(dy), L.ptr(z), L.ptr(dz), dy.numel(), _DT[dy.dtype], L.stream_ptr(dev))
-    L.check(rc, "vs_gelu_backward")
+    L.call("vs_gelu_backward", dev, L.ptr(dy), L.ptr(z), L.ptr(dz), dy.numel(), _DT[dy.dtype])
     return dz
 
 
@@ -865,14 +775,10 @@ def layernorm_backward(dout: torch.Tensor, x: torch.Tensor, w: torch.Tensor, b: 
         mod_ld = scale.stride(0)
         # dscale / dshift are written with the row stride of `scale`: allocate [G, mod_ld] when the rows are wider than C
         dscale, dshift = torch.zeros((2, scale.shape[0], mod_ld if mod_ld != Cc else Cc), dtype=torch.float32, device=dev).unbind(0)
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_layernorm_backward_ex(L.ptr(dout), dout.stride(-2), _DT3[dout.dtype], L.ptr(x), x.stride(0), L.ptr(w), L.ptr(b),
-                                              L.ptr(scale), mod_rows, mod_ld, L.ptr(dx), dx.stride(0), L.ptr(dx_add),
-                                              dx_add.stride(0) if dx_add is not None else 0, L.ptr(dx16),
-                                              dx16.stride(0) if dx16 is not None else 0, _DT[dx16.dtype] if dx16 is not None else 0,
-                                              L.ptr(dw), L.ptr(db), L.ptr(dscale), L.ptr(dshift), M, Cc, eps, grp_in, grp_out, grp_off,
-                                              L.stream_ptr(dev))
-    L.check(rc, "vs_layernorm_backward")
+    L.call("vs_layernorm_backward_ex", dev, L.ptr(dout), dout.stride(-2), _DT3[dout.dtype], L.ptr(x), x.stride(0), L.ptr(w), L.ptr(b), L.ptr(scale),
+           mod_rows, mod_ld, L.ptr(dx), dx.stride(0), L.ptr(dx_add), dx_add.stride(0) if dx_add is not None else 0, L.ptr(dx16),
+           dx16.stride(0) if dx16 is not None else 0, _DT[dx16.dtype] if dx16 is not None else 0, L.ptr(dw), L.ptr(db), L.ptr(dscale), L.ptr(dshift),
+           M, Cc, eps, grp_in, grp_out, grp_off)
     if dscale is not None and dscale.shape[1] != Cc:
         dscale, dshift = dscale[:, :Cc], dshift[:, :Cc]
     return dx, dw, db, dscale, dshift
@@ -923,9 +829,7 @@ def relu_mask_(dx: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     """In place dx = x > 0 ? dx : 0 (contiguous 16-bit, same shape): backward of a ReLU applied to x."""
     dev = L.require_device(dx, x)
     assert dx.shape == x.shape and dx.dtype == x.dtype and dx.is_contiguous() and x.is_contiguous()
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_relu_mask16(L.ptr(dx), L.ptr(x), dx.numel(), L.stream_ptr(dev))
-    L.check(rc, "vs_relu_mask16")
+    L.call("vs_relu_mask16", dev, L.ptr(dx), L.ptr(x), dx.numel())
     return dx
 
 
@@ -935,13 +839,9 @@ def relu_mask(dy: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     assert dy.shape == x.shape and dy.dtype == x.dtype and dy.is_contiguous() and x.is_contiguous()
     out = torch.empty_like(dy)
     if x.dtype == torch.float32:
-        with torch.cuda.device(dev):
-            rc = L.lib().vs_relu_mask_f32(L.ptr(dy), L.ptr(x), L.ptr(out), dy.numel(), L.stream_ptr(dev))
-        L.check(rc, "vs_relu_mask_f32")
+        L.call("vs_relu_mask_f32", dev, L.ptr(dy), L.ptr(x), L.ptr(out), dy.numel())
         return out
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_relu_mask16_to(L.ptr(dy), L.ptr(x), L.ptr(out), dy.numel(), L.stream_ptr(dev))
-    L.check(rc, "vs_relu_mask16_to")
+    L.call("vs_relu_mask16_to", dev, L.ptr(dy), L.ptr(x), L.ptr(out), dy.numel())
     return out
 
 
@@ -967,16 +867,13 @@ def gemm_wgrad(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, ksplit: int,
     M, N = a.shape[-2], w.shape[-2]
     ntaps = 0 if shifts is None else len(shifts)
     assert out.shape == ((M, N) if shifts is None else (ntaps, M, N))
-    import ctypes
     sh = None if shifts is None else (ctypes.c_int32 * ntaps)(*shifts)
     ws, ws_bytes = None, 0
     if workspace:
         ws = torch.empty(max(2, ksplit) * max(1, ntaps) * M * N, dtype=torch.float32, device=dev)
         ws_bytes = ws.numel() * 4
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_gemm_wgrad(L.ptr(a), L.ptr(w), L.ptr(out), M, N, K, a.stride(-2), w.stride(-2), N, asl, wsl, M * N, sh, ntaps,
-                                   ksplit, _DT[a.dtype], L.ptr(ws), ws_bytes, int(accumulate), L.stream_ptr(dev))
-    L.check(rc, "vs_gemm_wgrad")
+    L.call("vs_gemm_wgrad", dev, L.ptr(a), L.ptr(w), L.ptr(out), M, N, K, a.stride(-2), w.stride(-2), N, asl, wsl, M * N, sh, ntaps, ksplit,
+           _DT[a.dtype], L.ptr(ws), ws_bytes, int(accumulate))
     return out
 
 
@@ -991,10 +888,8 @@ def gemm_wgrad_tn(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, ksplit: i
     if workspace:
         ws = torch.empty(ksplit * M * N, dtype=torch.float32, device=dev)
         ws_bytes = ws.numel() * 4
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_gemm_wgrad_tn(L.ptr(a), L.ptr(w), L.ptr(out), M, N, Kred, a.stride(0), w.stride(0), N, ksplit, _DT[a.dtype],
-                                      L.ptr(ws), ws_bytes, int(accumulate), L.stream_ptr(dev))
-    L.check(rc, "vs_gemm_wgrad_tn")
+    L.call("vs_gemm_wgrad_tn", dev, L.ptr(a), L.ptr(w), L.ptr(out), M, N, Kred, a.stride(0), w.stride(0), N, ksplit, _DT[a.dtype], L.ptr(ws),
+           ws_bytes, int(accumulate))
     return out
 
 
@@ -1003,10 +898,8 @@ def gemm_splitk_accumulate(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, 
     dev = L.require_device(a, w, out)
     assert a.dtype == w.dtype and a.stride(1) == 1 and w.stride(1) == 1 and out.dtype == torch.float32
     K = a.shape[1] if K is None else K
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_gemm_splitk_accumulate(L.ptr(a), L.ptr(w), L.ptr(out), a.shape[0], w.shape[0], K, a.stride(0), w.stride(0),
-                                               out.stride(0), ksplit, _DT[a.dtype], L.stream_ptr(dev))
-    L.check(rc, "vs_gemm_splitk_accumulate")
+    L.call("vs_gemm_splitk_accumulate", dev, L.ptr(a), L.ptr(w), L.ptr(out), a.shape[0], w.shape[0], K, a.stride(0), w.stride(0), out.stride(0),
+           ksplit, _DT[a.dtype])
     return out
 
 
@@ -1036,10 +929,8 @@ def conv3x3_backward(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, *, relu
         ks, _ = wgrad_ksplit(256 if G > 1 else r256(Cin), r256(Cout), P, groups if G > 1 else 9)
         dw9 = torch.empty((9, Cin, Cout), dtype=torch.float32, device=dev)
         ws = torch.empty(ks * 9 * Cin * Cout, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = L.lib().vs_conv3x3_wgrad_tn(L.ptr(x), L.ptr(dy), L.ptr(dw9), N, H, W, Cin, Cout, int(relu_in), ks, _DT[dt], L.ptr(ws),
-                                             ws.numel() * 4, 0, L.stream_ptr(dev))
-        L.check(rc, "vs_conv3x3_wgrad_tn")
+        L.call("vs_conv3x3_wgrad_tn", dev, L.ptr(x), L.ptr(dy), L.ptr(dw9), N, H, W, Cin, Cout, int(relu_in), ks, _DT[dt], L.ptr(ws), ws.numel() * 4,
+               0)
         dw = dw9.view(3, 3, Cin, Cout).permute(3, 0, 1, 2).contiguous()            # [Cout, ky, kx, Cin]
         return dx, dw, (colsum(dy.view(P, Cout)) if need_db else None)
     # weight gradient: dY^T [Cout, pixels] and X^T [Cin, pixels] over the zero-bordered pixel grid, produced straight from the
@@ -1072,13 +963,9 @@ def upsample2x_backward_nhwc(dout: torch.Tensor) -> torch.Tensor:
     N, Ho, Wo, Cc = dout.shape
     din = torch.empty((N, Ho // 2, Wo // 2, Cc), dtype=dout.dtype, device=dev)
     if dout.dtype == torch.float32:
-        with torch.cuda.device(dev):
-            rc = L.lib().vs_upsample2x_backward_f32_nhwc(L.ptr(dout), L.ptr(din), N, Ho // 2, Wo // 2, Cc, L.stream_ptr(dev))
-        L.check(rc, "vs_upsample2x_backward_f32_nhwc")
+        L.call("vs_upsample2x_backward_f32_nhwc", dev, L.ptr(dout), L.ptr(din), N, Ho // 2, Wo // 2, Cc)
         return din
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_upsample2x_backward_nhwc(L.ptr(dout), L.ptr(din), N, Ho // 2, Wo // 2, Cc, _DT[dout.dtype], L.stream_ptr(dev))
-    L.check(rc, "vs_upsample2x_backward_nhwc")
+    L.call("vs_upsample2x_backward_nhwc", dev, L.ptr(dout), L.ptr(din), N, Ho // 2, Wo // 2, Cc, _DT[dout.dtype])
     return din
 
 
@@ -1117,9 +1004,7 @@ def transpose_f32(x: torch.Tensor, pad_to: int = 64, *, relu: bool = False, conv
         out = torch.empty((Cc, Rpad), dtype=torch.float32, device=dev)
     h, w = conv_hw if conv_hw is not None else (0, 0)
     dy, dx = (2, 0) if border else tap
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_transpose_f32(L.ptr(x), x.stride(0), L.ptr(out), out.stride(0), Rb, Cc, Rpad, int(relu), h, w, dy, dx, L.ptr(colsum), L.stream_ptr(dev))
-    L.check(rc, "vs_transpose_f32")
+    L.call("vs_transpose_f32", dev, L.ptr(x), x.stride(0), L.ptr(out), out.stride(0), Rb, Cc, Rpad, int(relu), h, w, dy, dx, L.ptr(colsum))
     return out
 
 
@@ -1135,10 +1020,8 @@ def transpose_pack_split(x: torch.Tensor, pad_to: int = 64, *, relu: bool = Fals
     h, w = conv_hw if conv_hw is not None else (0, 0)
     if border:
         tap = (2, 0)
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_transpose_pack_split(L.ptr(x), x.stride(0), L.ptr(out), out.stride(0), R, Cc, Rpad, int(relu), h, w, tap[0], tap[1], scale_exp,
-                                             L.ptr(colsum), L.stream_ptr(dev))
-    L.check(rc, "vs_transpose_pack_split")
+    L.call("vs_transpose_pack_split", dev, L.ptr(x), x.stride(0), L.ptr(out), out.stride(0), R, Cc, Rpad, int(relu), h, w, tap[0], tap[1], scale_exp,
+           L.ptr(colsum))
     return SplitWeight(out, 2.0 ** (-scale_exp), (Cc, Rpad))
 
 
@@ -1148,9 +1031,7 @@ def split16(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == torch.float32 and x.shape[1] % 8 == 0
     hi = torch.empty(x.shape, dtype=torch.float16, device=dev)
     lo = torch.empty_like(hi)
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_split16(L.ptr(x), x.stride(0), L.ptr(hi), L.ptr(lo), hi.stride(0), x.shape[0], x.shape[1], L.stream_ptr(dev))
-    L.check(rc, "vs_split16")
+    L.call("vs_split16", dev, L.ptr(x), x.stride(0), L.ptr(hi), L.ptr(lo), hi.stride(0), x.shape[0], x.shape[1])
     return hi, lo
 
 
@@ -1165,13 +1046,10 @@ def gemm_wgrad_split(a: torch.Tensor, w: SplitWeight, out: torch.Tensor, ksplit:
     ntaps = 0 if shifts is None else len(shifts)
     assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == ((M, N) if shifts is None else (ntaps, M, N))
     assert K % (64 * ksplit) == 0, (K, ksplit)
-    import ctypes
     sh = None if shifts is None else (ctypes.c_int32 * ntaps)(*shifts)
     ws = torch.empty(max(2, ksplit) * max(1, ntaps) * M * N, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_gemm_wgrad(L.ptr(a), L.ptr(wd), L.ptr(out), M, N, K, a.stride(0), wd.stride(0), N, 0, 0, M * N, sh, ntaps, ksplit, 4, L.ptr(ws),
-                                   ws.numel() * 4, 0, L.stream_ptr(dev))
-    L.check(rc, "vs_gemm_wgrad(split)")
+    L.call("vs_gemm_wgrad", dev, L.ptr(a), L.ptr(wd), L.ptr(out), M, N, K, a.stride(0), wd.stride(0), N, 0, 0, M * N, sh, ntaps, ksplit, 4, L.ptr(ws),
+           ws.numel() * 4, 0)
     if w.acc_scale != 1.0:
         out.mul_(w.acc_scale)
     return out
@@ -1188,10 +1066,8 @@ def gemm_wgrad_split_atn(a: torch.Tensor, w: SplitWeight, out: torch.Tensor, ksp
     assert Kpad >= Kred and Kpad % (64 * ksplit) == 0 and M % 256 == 0 and N % 256 == 0, (a.shape, wd.shape, ksplit)
     assert out.dtype == torch.float32 and out.stride(1) == 1 and out.shape == ((N, M) if transpose_out else (M, N))
     ws = torch.empty(ksplit * M * N, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_gemm_wgrad_split_atn(L.ptr(a), L.ptr(wd), L.ptr(out), M, N, Kred, Kpad, a.stride(0), wd.stride(0), out.stride(0), ksplit,
-                                             int(transpose_out), L.ptr(ws), ws.numel() * 4, 0, L.stream_ptr(dev))
-    L.check(rc, "vs_gemm_wgrad_split_atn")
+    L.call("vs_gemm_wgrad_split_atn", dev, L.ptr(a), L.ptr(wd), L.ptr(out), M, N, Kred, Kpad, a.stride(0), wd.stride(0), out.stride(0), ksplit,
+           int(transpose_out), L.ptr(ws), ws.numel() * 4, 0)
     if w.acc_scale != 1.0:
         out.mul_(w.acc_scale)
     return out
@@ -1286,14 +1162,12 @@ def head1x1_backward(dy: torch.Tensor, t: torch.Tensor, w: torch.Tensor, *, relu
     dt = torch.empty_like(t)
     dw_part = torch.empty((nwg, rows, Cin), dtype=torch.float32, device=dev)
     db_part = torch.empty((nwg, rows), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        if split:
-            rc = L.lib().vs_head1x1_backward_split(L.ptr(dy), ldy, L.ptr(t), L.ptr(w), int(scale_exp), L.ptr(dt), L.ptr(dw_part), L.ptr(db_part), P, Cin,
-                                                   Cout, int(relu), nwg, L.stream_ptr(dev))
-        else:
-            rc = L.lib().vs_head1x1_backward16(L.ptr(dy), ldy, L.ptr(t), L.ptr(w), L.ptr(dt), L.ptr(dw_part), L.ptr(db_part), P, Cin, Cout, int(relu),
-                                               nwg, _DTX[dy.dtype], L.stream_ptr(dev))
-    L.check(rc, "vs_head1x1_backward")
+    if split:
+        L.call("vs_head1x1_backward_split", dev, L.ptr(dy), ldy, L.ptr(t), L.ptr(w), int(scale_exp), L.ptr(dt), L.ptr(dw_part), L.ptr(db_part), P, Cin,
+               Cout, int(relu), nwg)
+    else:
+        L.call("vs_head1x1_backward16", dev, L.ptr(dy), ldy, L.ptr(t), L.ptr(w), L.ptr(dt), L.ptr(dw_part), L.ptr(db_part), P, Cin, Cout, int(relu),
+               nwg, _DTX[dy.dtype])
     return dt, dw_part.sum(0)[:Cout].contiguous(), db_part.sum(0)[:Cout].contiguous()
 
 
@@ -1328,13 +1202,10 @@ def attention_backward_split(qkv_q: torch.Tensor, qkv_k: torch.Tensor, qkv_v: to
     for t in (dq, dk, dv):
         assert t.dtype == torch.float32 and t.stride(1) == 1
     delta = torch.empty((qkv_q.shape[0], H), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_attention_backward_split(L.ptr(qh), L.ptr(ql), L.ptr(kh), L.ptr(kl), L.ptr(vh), L.ptr(vl), L.ptr(dh), L.ptr(dl), L.ptr(out),
-                                                 L.ptr(dout), L.ptr(lse), L.ptr(delta), L.ptr(dq), L.ptr(dk), L.ptr(dv), nbatch, H, Lq, Lk, q_batch_rows,
-                                                 k_batch_rows, qh.stride(0), kh.stride(0), vh.stride(0), dh.stride(0), out.stride(0), dout.stride(0),
-                                                 dq.stride(0), dk.stride(0), dv.stride(0), L.ptr(kv_seg), L.ptr(q_kvlen), max_keys, scale,
-                                                 L.stream_ptr(dev))
-    L.check(rc, "vs_attention_backward_split")
+    L.call("vs_attention_backward_split", dev, L.ptr(qh), L.ptr(ql), L.ptr(kh), L.ptr(kl), L.ptr(vh), L.ptr(vl), L.ptr(dh), L.ptr(dl), L.ptr(out),
+           L.ptr(dout), L.ptr(lse), L.ptr(delta), L.ptr(dq), L.ptr(dk), L.ptr(dv), nbatch, H, Lq, Lk, q_batch_rows, k_batch_rows, qh.stride(0),
+           kh.stride(0), vh.stride(0), dh.stride(0), out.stride(0), dout.stride(0), dq.stride(0), dk.stride(0), dv.stride(0), L.ptr(kv_seg),
+           L.ptr(q_kvlen), max_keys, scale)
     return dq, dk, dv
 
 
@@ -1351,10 +1222,7 @@ def conv3x3_wgrad_split_stream(dy: torch.Tensor, x: torch.Tensor, *, relu_in: bo
     workers = max(8, min(torch.cuda.get_device_properties(dev).multi_processor_count // nblk, (items + 7) // 8 * 8) // 8 * 8)
     dw_part = torch.empty((workers, 9, Cin, Cout), dtype=torch.float32, device=dev)
     db_part = torch.empty((workers, Cout), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_conv3x3_wgrad_split_stream(L.ptr(x), L.ptr(dy), L.ptr(dw_part), L.ptr(db_part), N, H, W, Cin, Cout, int(relu_in), workers,
-                                                   L.stream_ptr(dev))
-    L.check(rc, "vs_conv3x3_wgrad_split_stream")
+    L.call("vs_conv3x3_wgrad_split_stream", dev, L.ptr(x), L.ptr(dy), L.ptr(dw_part), L.ptr(db_part), N, H, W, Cin, Cout, int(relu_in), workers)
     return dw_part.sum(0), db_part.sum(0)
 
 
@@ -1392,10 +1260,8 @@ def conv3x3_backward_split(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, *
         dyTp = transpose_pack_split(dy.view(P, Cout), 64 * ks, colsum=db)                                   # [Cout, Ppad] packed
         dw9 = torch.empty((9, Cin, Cout), dtype=torch.float32, device=dev)
         ws = torch.empty(ks * 9 * Cin * Cout, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = L.lib().vs_conv3x3_wgrad_split_atn(L.ptr(x), L.ptr(dyTp.data), L.ptr(dw9), N, H, W, Cin, Cout, dyTp.data.shape[1], dyTp.data.stride(0),
-                                                    int(relu_in), ks, L.ptr(ws), ws.numel() * 4, 0, L.stream_ptr(dev))
-        L.check(rc, "vs_conv3x3_wgrad_split_atn")
+        L.call("vs_conv3x3_wgrad_split_atn", dev, L.ptr(x), L.ptr(dyTp.data), L.ptr(dw9), N, H, W, Cin, Cout, dyTp.data.shape[1], dyTp.data.stride(0),
+               int(relu_in), ks, L.ptr(ws), ws.numel() * 4, 0)
         return dx, dw9.view(3, 3, Cin, Cout).permute(3, 2, 0, 1).contiguous(), db
     if Cin % 64 == 0 and Cout % 64 == 0 and W % 32 == 0:
         # narrow layers (the pts3d head's 256 -> 128 and 128 -> 128 convolutions): one streaming pass over X and dY as they are
@@ -1424,7 +1290,6 @@ def conv3x3_backward_split(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, *
 def sustained_mfma_tflops(device, ms_target: float = 40.0) -> float:
     """TFLOP/s the chip sustains on back-to-back v_mfma_f32_16x16x32_f16 with register operands holding random data and no memory traffic
     (vs_probe_mfma_rate): the power-limited ceiling of every 16-bit MFMA kernel on this device, measured, beside the 2.5 PFLOP/s headline."""
-    import ctypes
     dev = torch.device(device)
     src = (torch.rand(1 << 19, device=dev) * 4 - 2).half()
     scratch = torch.empty(512 * 256, dtype=torch.float32, device=dev)
@@ -1433,9 +1298,8 @@ def sustained_mfma_tflops(device, ms_target: float = 40.0) -> float:
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         with torch.cuda.device(dev):
             s.record()
-            rc = L.lib().vs_probe_mfma_rate(L.ptr(src), L.ptr(scratch), iters, ctypes.byref(fl), L.stream_ptr(dev))
+            L.call("vs_probe_mfma_rate", dev, L.ptr(src), L.ptr(scratch), iters, ctypes.byref(fl))
             e.record()
-        L.check(rc, "vs_probe_mfma_rate")
         e.synchronize()
         return s.elapsed_time(e), fl.value
     ms, f = run(20000)                                   # warm-up and calibration (clocks settle within a few ms)
@@ -1446,7 +1310,6 @@ def sustained_mfma_tflops(device, ms_target: float = 40.0) -> float:
 
 def _ssim_args(x: torch.Tensor, y: torch.Tensor, taps):
     """(x, y, host taps) of the SSIM kernels: f32 NCHW contiguous device tensors of one shape, taps a ctypes float array."""
-    import ctypes
     if x.shape != y.shape or x.dim() != 4:
         raise ValueError(f"SSIM kernels take two [N, C, H, W] tensors of one shape, got {tuple(x.shape)} and {tuple(y.shape)}")
     dev = L.require_device(x, y)
@@ -1463,16 +1326,12 @@ def ssim_forward(x: torch.Tensor, y: torch.Tensor, taps, cov_norm: float, c1: fl
     dev, x, y, tp, ws = _ssim_args(x, y, taps)
     N, C, H, W = x.shape
     flags = (L.VS_SSIM_COMPONENTS if components else 0) | (L.VS_SSIM_UNIT_WINDOW if unit_window else 0)
-    nbytes = L.lib().vs_ssim_workspace_bytes(N, C, H, W, ws, flags)
-    L.check(nbytes, "vs_ssim_workspace_bytes")
+    nbytes = L.call("vs_ssim_workspace_bytes", dev, N, C, H, W, ws, flags)
     nq = 4 if components else 1
     work = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
     per_plane = torch.empty((nq, N, C), dtype=torch.float32, device=dev)
     per_image = torch.empty((nq, N), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_ssim_forward(L.ptr(x), L.ptr(y), N, C, H, W, tp, ws, cov_norm, c1, c2, flags, L.ptr(work),
-                                     L.ptr(per_plane), L.ptr(per_image), L.stream_ptr(dev))
-    L.check(rc, "vs_ssim_forward")
+    L.call("vs_ssim_forward", dev, L.ptr(x), L.ptr(y), N, C, H, W, tp, ws, cov_norm, c1, c2, flags, L.ptr(work), L.ptr(per_plane), L.ptr(per_image))
     return per_plane, per_image
 
 
@@ -1488,11 +1347,8 @@ def ssim_backward(x: torch.Tensor, y: torch.Tensor, taps, cov_norm: float, c1: f
     dy = torch.empty_like(y) if need_dy else None
     if dx is None and dy is None:
         return None, None
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_ssim_backward(L.ptr(x), L.ptr(y), N, C, H, W, tp, ws, cov_norm, c1, c2,
-                                      L.VS_SSIM_UNIT_WINDOW if unit_window else 0, L.ptr(gs), L.ptr(gt), L.ptr(dx),
-                                      L.ptr(dy), L.stream_ptr(dev))
-    L.check(rc, "vs_ssim_backward")
+    L.call("vs_ssim_backward", dev, L.ptr(x), L.ptr(y), N, C, H, W, tp, ws, cov_norm, c1, c2, L.VS_SSIM_UNIT_WINDOW if unit_window else 0, L.ptr(gs),
+           L.ptr(gt), L.ptr(dx), L.ptr(dy))
     return dx, dy
 
 
@@ -1506,7 +1362,6 @@ def lpips_scale_log2(H: int, W: int) -> int:
 
 
 def _ptr_array(ts):
-    import ctypes
     return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
 
 
@@ -1516,9 +1371,7 @@ def lpips_prep(img: torch.Tensor, normalize: bool) -> torch.Tensor:
     img = img.contiguous().float()
     N, _, H, W = img.shape
     out = torch.empty((N, H, W, 32), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_lpips_prep(L.ptr(img), N, H, W, int(normalize), L.ptr(out), L.stream_ptr(dev))
-    L.check(rc, "vs_lpips_prep")
+    L.call("vs_lpips_prep", dev, L.ptr(img), N, H, W, int(normalize), L.ptr(out))
     return out
 
 
@@ -1528,9 +1381,7 @@ def lpips_prep_backward(g32: torch.Tensor, g: torch.Tensor, normalize: bool) -> 
     N, H, W, _ = g32.shape
     g = g.detach().reshape(N).contiguous().float()
     out = torch.empty((N, 3, H, W), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_lpips_prep_backward(L.ptr(g32), L.ptr(g), N, H, W, int(normalize), lpips_scale_log2(H, W), L.ptr(out), L.stream_ptr(dev))
-    L.check(rc, "vs_lpips_prep_backward")
+    L.call("vs_lpips_prep_backward", dev, L.ptr(g32), L.ptr(g), N, H, W, int(normalize), lpips_scale_log2(H, W), L.ptr(out))
     return out
 
 
@@ -1539,9 +1390,7 @@ def lpips_maxpool(x: torch.Tensor) -> torch.Tensor:
     dev = L.require_device(x)
     N, H, W, C = x.shape
     y = torch.empty((N, H // 2, W // 2, C), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_lpips_maxpool(L.ptr(x), N, H, W, C, L.ptr(y), L.stream_ptr(dev))
-    L.check(rc, "vs_lpips_maxpool")
+    L.call("vs_lpips_maxpool", dev, L.ptr(x), N, H, W, C, L.ptr(y))
     return y
 
 
@@ -1550,9 +1399,7 @@ def lpips_maxpool_backward(dy: torch.Tensor, x: torch.Tensor, g_add: Optional[to
     dev = L.require_device(dy, x, g_add)
     N, H, W, C = x.shape
     dx = torch.empty_like(x)
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_lpips_maxpool_backward(L.ptr(dy), L.ptr(x), L.ptr(g_add), N, H, W, C, L.ptr(dx), L.stream_ptr(dev))
-    L.check(rc, "vs_lpips_maxpool_backward")
+    L.call("vs_lpips_maxpool_backward", dev, L.ptr(dy), L.ptr(x), L.ptr(g_add), N, H, W, C, L.ptr(dx))
     return dx
 
 
@@ -1560,13 +1407,10 @@ def lpips_head_forward(taps0, taps1, lins) -> torch.Tensor:
     """Per-image LPIPS distance [N] f32 from the five taps of both images (NHWC f32) and the five lin weights (vs_lpips_head_forward)."""
     dev = L.require_device(*taps0, *taps1, *lins)
     N, H, W, _ = taps0[0].shape
-    nbytes = L.check(L.lib().vs_lpips_workspace_bytes(N, H, W), "vs_lpips_workspace_bytes")
+    nbytes = L.call("vs_lpips_workspace_bytes", dev, N, H, W)
     work = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
     out = torch.empty(N, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_lpips_head_forward(_ptr_array(taps0), _ptr_array(taps1), _ptr_array(lins), N, H, W, L.ptr(work), L.ptr(out),
-                                           L.stream_ptr(dev))
-    L.check(rc, "vs_lpips_head_forward")
+    L.call("vs_lpips_head_forward", dev, _ptr_array(taps0), _ptr_array(taps1), _ptr_array(lins), N, H, W, L.ptr(work), L.ptr(out))
     return out
 
 
@@ -1578,8 +1422,6 @@ def lpips_head_backward(taps0, taps1, lins, g: torch.Tensor, need0: bool, need1:
     g = g.detach().reshape(N).contiguous().float()
     d0 = [torch.empty_like(t) for t in taps0] if need0 else None
     d1 = [torch.empty_like(t) for t in taps1] if need1 else None
-    with torch.cuda.device(dev):
-        rc = L.lib().vs_lpips_head_backward(_ptr_array(taps0), _ptr_array(taps1), _ptr_array(lins), L.ptr(g), N, H, W, lpips_scale_log2(H, W),
-                                            None if d0 is None else _ptr_array(d0), None if d1 is None else _ptr_array(d1), L.stream_ptr(dev))
-    L.check(rc, "vs_lpips_head_backward")
+    L.call("vs_lpips_head_backward", dev, _ptr_array(taps0), _ptr_array(taps1), _ptr_array(lins), L.ptr(g), N, H, W, lpips_scale_log2(H, W),
+           None if d0 is None else _ptr_array(d0), None if d1 is None else _ptr_array(d1))
     return d0, d1

@@ -74,7 +74,6 @@ def _forward_impl(means3D, cov3D, shs, colors_precomp, opacities, viewmatrix, pr
                   cam_scene, H, W, sh_degree, flags):
     """Calls vs_raster_forward; returns (outputs, state) where state keeps every device buffer alive."""
     dev = L.require_device(means3D, cov3D, shs, colors_precomp, opacities, viewmatrix, projmatrix, campos, tanfov, background)
-    lib = L.lib()
     S, P = means3D.shape[0], means3D.shape[1]
     Cn = viewmatrix.shape[0]
     cov33 = cov3D.dim() == 4
@@ -100,10 +99,10 @@ def _forward_impl(means3D, cov3D, shs, colors_precomp, opacities, viewmatrix, pr
     out = L.VsRasterOut()
     out.color, out.depth, out.opacity, out.radii, out.n_touched = L.ptr(color), L.ptr(depth), L.ptr(opacity), L.ptr(radii), L.ptr(n_touched)
     alloc = L.TorchAllocator(dev)
-    with torch.cuda.device(dev):
-        R = lib.vs_raster_forward(C.byref(inp), C.byref(out), alloc.fn, None, L.stream_ptr(dev))
-    alloc.fn = None  # break the allocator <-> ctypes-callback reference cycle so the buffers die with their last user
-    L.check(R, "vs_raster_forward")
+    try:
+        R = L.call("vs_raster_forward", dev, C.byref(inp), C.byref(out), alloc.fn, None)
+    finally:
+        alloc.fn = None  # break the allocator <-> ctypes-callback reference cycle so the buffers die with their last user
     if n_touched is None:
         n_touched = torch.zeros((Cn, P), dtype=torch.int32, device=dev)
     _hint.last = dict(num_rendered=int(R), misc=alloc.tensors[L.VS_BUF_MISC].view(torch.int64)[:4])
@@ -172,12 +171,11 @@ def backward_debug(fwd: dict, dL_dcolor, dL_ddepth=None) -> dict:
 def _backward_impl(inp, out, grads, dev) -> None:
     """Calls vs_raster_backward (its scratch -- the per-(camera, Gaussian) gradient records -- comes from torch's caching allocator and goes
     back to it on return).  A module-level function so that bench.py can bracket it with events."""
-    lib = L.lib()
     alloc = L.TorchAllocator(dev)
-    with torch.cuda.device(dev):
-        rc = lib.vs_raster_backward(C.byref(inp), C.byref(out), C.byref(grads), alloc.fn, None, L.stream_ptr(dev))
-    alloc.fn = None
-    L.check(rc, "vs_raster_backward")
+    try:
+        L.call("vs_raster_backward", dev, C.byref(inp), C.byref(out), C.byref(grads), alloc.fn, None)
+    finally:
+        alloc.fn = None
 
 
 class _Rasterize(torch.autograd.Function):
@@ -213,9 +211,6 @@ class _Rasterize(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_color, g_radii, g_depth, g_opacity, g_touched):
-        lib = L.lib()
-        if not hasattr(lib, "vs_raster_backward"):
-            raise RuntimeError("libvicasplat_hip.so was built without vs_raster_backward")
         (means3D, cov3D, shs, colors_precomp, opacities, viewmatrix, projmatrix, campos, tanfov, background, cam_scene,
          projmatrix_raw) = ctx.keep
         radii, color, depth = ctx.saved_tensors    # keeps the buffers behind ctx.out.radii / color / depth alive
