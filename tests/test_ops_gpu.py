@@ -312,7 +312,8 @@ def test_gaussian_adapter_fused(dt, layout):
     gs = (torch.randn(N, 83, H, W, device=d) * 2.0).to(dt)
     if layout == "nhwc":
         pts_in, gs_in = pts.contiguous(memory_format=torch.channels_last), gs.contiguous(memory_format=torch.channels_last)
-    else:  # a channel slice of a wider NHWC tensor: pixel stride != channel count -> generic kernel
+    else:  # a channel slice of a wider NHWC tensor: gs_ch == 1, gs_pix == 90 >= 83 and <= 96, 64 * 90 % 8 == 0 -> still the dense kernel
+        # (vs_gaussian_adapter's `dense16`), with a padded pixel stride; the stride-generic kernel is reached in test_adapter_edges_gpu.py
         wide = torch.zeros(N, 90, H, W, device=d, dtype=dt).contiguous(memory_format=torch.channels_last)
         wide[:, :83] = gs
         gs_in = wide[:, :83]

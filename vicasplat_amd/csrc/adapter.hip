@@ -262,7 +262,7 @@ __global__ void __launch_bounds__(64) adapter_nhwc16_kernel(const AdapterArgs a)
 // ---- backward of the adapter (training): gradients of the Gaussian attributes -> gradients of the two heads' 16-bit NHWC
 // outputs.  One wave per 64 consecutive pixels; the wide per-pixel gradient rows (harmonics 3*d_sh floats, raw 11+3*d_sh
 // floats) and the 16-bit outputs move through LDS as contiguous blocks, the per-pixel chain rule runs in registers:
-//   means  m = x k(d), k = expm1(d)/d            dx = g k + (g.x) k'(d) x / d
+//   means  m = x k(d), k = expm1(d)/max(d, 1e-8)  dx = g k + (g.x) k'(d) x / d    (below the clamp k'(d) = e^d / 1e-8)
 //   opacity p = sigmoid(o) [pdf->opacity map]     do = gp p (1-p) [* map']
 //   scale   s = min(0.001 softplus(v), 0.3) ...   dv = gs ds/dv
 //   cov     = (R S)(R S)^T                         dRS = (G + G^T) RS,  ds_c = sum_r dRS_rc R_rc,  dR_rc = dRS_rc s_c
@@ -324,9 +324,10 @@ __global__ void __launch_bounds__(64) adapter_backward_kernel(const AdapterBwdAr
             const float em = expm1f(d), k = em / d, kp = ((em + 1.0f) * d - em) / (d * d);
             const float gx = (gm[0] * x + gm[1] * y + gm[2] * z) * kp / d;
             dpt[0] = gm[0] * k + gx * x; dpt[1] = gm[1] * k + gx * y; dpt[2] = gm[2] * k + gx * z;
-        } else {   // m = x * expm1(d) / 1e-8 in this branch of the forward's clamp
+        } else {   // m = x * expm1(d) / 1e-8 in this branch of the forward's clamp: the clamp has no derivative, expm1(d) has
             const float k = expm1f(d) / 1e-8f;
-            dpt[0] = gm[0] * k; dpt[1] = gm[1] * k; dpt[2] = gm[2] * k;
+            const float gx = d > 0.f ? (gm[0] * x + gm[1] * y + gm[2] * z) / d * (expf(d) / 1e-8f) : 0.f;
+            dpt[0] = gm[0] * k + gx * x; dpt[1] = gm[1] * k + gx * y; dpt[2] = gm[2] * k + gx * z;
         }
         // ---- opacity ----
         const float o_raw = cvtin<DT>(gg[0]);
@@ -474,9 +475,8 @@ extern "C" int vs_gaussian_adapter(const void *pts, int64_t pts_pix, int64_t pts
                          ((64 * pts_pix) % ev == 0) && ((64 * gs_pix) % ev == 0);
     if (dense16) {
         dim3 g64((unsigned)vs::cdiv64(npix, 64));
-        if (in_dtype == 0 && ((32 * pts_pix) % ev == 0) && ((32 * gs_pix) % ev == 0))
+        if (in_dtype == 0)   // 32-pixel blocks: 32 * stride floats are a whole number of 16-byte vectors for every stride
             hipLaunchKernelGGL((adapter_nhwc16_kernel<0, 32>), dim3((unsigned)vs::cdiv64(npix, 32)), dim3(64), 0, stream, a);
-        else if (in_dtype == 0) hipLaunchKernelGGL(adapter_nhwc16_kernel<0>, g64, dim3(64), 0, stream, a);
         else if (in_dtype == 1) hipLaunchKernelGGL(adapter_nhwc16_kernel<1>, g64, dim3(64), 0, stream, a);
         else hipLaunchKernelGGL(adapter_nhwc16_kernel<2>, g64, dim3(64), 0, stream, a);
         VS_HIP(hipGetLastError());
