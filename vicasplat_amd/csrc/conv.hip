@@ -1102,7 +1102,7 @@ static int conv3x3_entry(const void *in, const void *w, const float *bias, const
     const long long big = vs::cdiv64(M, 256) * vs::cdiv(Cout, BN);
     if (dtype == 4) {
         VS_CHECK(Cin % 64 == 0, "vs_conv3x3_split_nhwc: Cin must be a multiple of 32");
-        if (cshift >= 0 && Cout % 128 == 0 && Cout % 256 != 0 && (9 * Cin / 64) % 2 == 0 && big >= 224) {   // (Cout = 256 maps too small for the 256 x 256 kernel: the 4-wave kernel is 8 % faster there, measured)
+        if (cshift >= 0 && Cout % 128 == 0 && Cout % 256 != 0 && (9 * Cin / 64) % 2 == 0 && big >= 224) {   // `big >= 224` has a twin, PACKED_CONV_MIN_PIXELS in model/encoder/heads/dpt.py: change both.  (Cout = 256 maps too small for the 256 x 256 kernel: the 4-wave kernel is 8 % faster there, measured)
             dim3 grid((unsigned)(vs::cdiv64(M, 256) * (Cout / 128))), block(512);
             if (g.a_packed) hipLaunchKernelGGL((conv3x3_256x128_split_kernel<false, false, true>), grid, block, 0, stream, g, 1 << cshift);
             else if (relu_in) hipLaunchKernelGGL((conv3x3_256x128_split_kernel<true, false>), grid, block, 0, stream, g, 1 << cshift);

@@ -2,18 +2,61 @@
 (gaussian_param_head).  Reference: heads/dpt_block.py:79-218,264-419, heads/dpt_head.py:21-119,
 heads/dpt_gs_head.py:98-206, heads/postprocess.py:10-63.  Parameter names == the reference's state_dict keys.
 
-SURVEY.md 8(f)-1: the heads are 42 % of the forward FLOPs.  All 3x3 / 1x1 / transposed convolutions and the
-bilinear upsampling run on the hand-written HIP kernels (implicit-GEMM MFMA conv, GEMM, upsample) on NHWC 16-bit
-activations; the 7x7 RGB stem conv is a window GEMM on the same main loop (`vs_conv7x7_rgb_nhwc`; im2col + GEMM on the f32 / split paths).  HIP device tensors only.
+SURVEY.md 8(f)-1: the heads are 42 % of the forward FLOPs.  Every convolution, GEMM and bilinear x2 runs on the hand-written HIP kernels on
+NHWC activations (16-bit, or f32 in the f32 / split classes).  HIP device tensors only.  The trunk is one sequence for every operand class;
+the tail is a ROUTE that `pts3d_route` / `gs_route` name from Python values alone (no GPU, no library) and the forwards dispatch once:
+  pts3d  split_packed_dot   upsample2x(packed) -> [conv3x3 + ReLU + 1x1 as f32 dot products] in one kernel (split class)
+         fused16            upsample2x -> [conv3x3 + ReLU + 1x1] in one kernel (f16 / bf16)
+         unfused            upsample2x -> conv3x3 + ReLU -> GEMM
+  gs     split_stream_stem  streaming 7x7 stem that writes up2(trunk) + relu(stem) packed -> [conv3x3 + ReLU + 1x1] (split class)
+         split_stem_up      the same sum from the window-GEMM stem's epilogue -> the same head kernel
+         split_up_packed    stem map -> upsample2x(+ relu(stem), packed) -> the same head kernel
+         fused16 / unfused  stem map -> upsample2x(+ relu(stem)) -> [conv3x3 + ReLU + 1x1] (f16 / bf16) / conv3x3 + ReLU -> GEMM
+  stem map: "split7" (split-class window GEMM), "im2col_f32" (im2col + GEMM of the f32 class) or "window16" (16-bit window GEMM).
 """
 from __future__ import annotations
 
 import torch
-import torch.nn.functional as F      # F.pad / F.unfold of the exact-f32 class's im2col stem only -- no torch convolution / interpolation anywhere
+import torch.nn.functional as F      # F.pad / F.unfold of weight packing and the im2col stem only -- no torch convolution / interpolation anywhere
 from torch import nn
 
 from .... import ops
 
+# Twin of `big >= 224` in conv3x3_entry (csrc/conv.hip): in the split class a convolution with Cout % 128 == 0 && Cout % 256 != 0 (the pts3d
+# head's 256 -> 128) runs on a 256-pixel tile kernel, the only kind that reads a packed (hi, lo) input, from 224 tiles on -- so from this many
+# pixels on the trunk writes its last map packed.  If the two drift apart the library refuses the call ("a packed input is taken by the ...").
+PACKED_CONV_MIN_PIXELS = 224 * 256
+# K per tap of the fused conv3x3 -> 1x1 kernels in 2-byte units: `Cin == 64 << s` in vs_conv3x3_head1x1_nhwc (16-bit channels), `2 * Cin ==
+# 64 << s` in vs_conv3x3_head1x1_split_nhwc (f32 channels, two units each) -- ONE constraint: 64..512 16-bit or 32..256 f32 channels.
+_FUSED_HEAD_K_UNITS = (64, 128, 256, 512)
+_CLASS_OF = {torch.float16: "f16", torch.bfloat16: "bf16", torch.float32: "f32"}
+
+
+def pts3d_route(cls: str, BT: int, gh: int, gw: int, c_trunk: int, c_h0: int, c_h2: int):
+    """-> (route, trunk_packed: the trunk's last bilinear pass writes the packed (hi, lo) form) for operand class "f16" / "bf16" / "f32" / "split", BT
+    frames of gh x gw tokens, the channels of the trunk, head[0] and head[2].  The head's 256 * BT * gh * gw pixels always fill 256-pixel tiles."""
+    # head[0] then runs on the 256 x 128 tile kernel (conv3x3_entry: a whole, even number of K tiles); otherwise the trunk writes plain f32
+    trunk_packed = cls == "split" and c_h0 == 128 and c_trunk in (64, 128, 256) and BT * 64 * gh * gw >= PACKED_CONV_MIN_PIXELS
+    if c_h0 == 128 and cls == "split" and c_h2 == 128:
+        return "split_packed_dot", trunk_packed
+    return ("fused16" if c_h0 == 128 and cls in ("f16", "bf16") else "unfused"), trunk_packed     # (no other one-kernel form: conv3x3, then a GEMM)
+
+
+def gs_route(cls: str, gh: int, gw: int, H: int, W: int, num_channels: int, c_trunk: int, c_stem: int, c_h0: int):
+    """-> (route, stem) for H x W frames and the channels of the trunk, the 7x7 stem and head[0]; stem names the stem's kernel ("stream":
+    inside `split_stream_stem`).  BT * 16gh * 16gw pixels are a multiple of 256 for every batch and grid, so BT selects nothing."""
+    # the split window GEMM tiles Cout by 256: otherwise the split class takes the f32 class's im2col + GEMM, on split operands
+    stem = {"split": "split7" if c_stem % 256 == 0 else "im2col_f32", "f32": "im2col_f32"}.get(cls, "window16")
+    # otherwise two kernels: the fused 1x1 holds <= 96 output rows of a 256-wide 3x3, on a K it can tile; the f32 class has no such kernel
+    if cls == "f32" or num_channels > 96 or c_h0 != 256 or c_trunk * (2 if cls == "split" else 1) not in _FUSED_HEAD_K_UNITS:
+        return "unfused", stem
+    if cls != "split":
+        return "fused16", stem
+    # the stem's epilogue adds the trunk pixel for pixel; otherwise the stem is a map of its own (and upsample2x_nhwc refuses a mismatched one)
+    if stem != "split7" or c_trunk != c_stem or (16 * gh, 16 * gw) != (H, W):
+        return "split_up_packed", stem
+    # the streaming kernel walks 32-pixel column strips of a 256-channel stem; otherwise the window GEMM's epilogue forms the same sum
+    return ("split_stream_stem", "stream") if W % 32 == 0 and c_stem == 256 else ("split_stem_up", stem)
 
 
 def _no_torch_forward(self, *a, **k):
@@ -83,15 +126,11 @@ def _pad_to(n: int, m: int = 64) -> int:
 
 
 class PixelwiseTaskWithDPT(nn.Module):
-    """`.dpt` holds the parameters (reference naming: <head>.dpt.<...>).  The forward drives the hand-written HIP
-    kernels on NHWC 16-bit activations:
-      * every 3x3 convolution (layer_rn, the 16 ResidualConvUnit convs, head convs, the stride-2 reassemble conv) is the
-        implicit-GEMM MFMA kernel `vs_conv3x3_nhwc` with pre-activation ReLU / bias / residual / ReLU fused;
-      * every 1x1 convolution and both ConvTranspose2d(k == stride) layers are plain GEMMs (`vs_gemm_bias_act`) -- tokens
-        [BT, 256, C] ARE an NHWC 16x16 map, so no reshape copy is needed on the way in;
-      * bilinear x2 (align_corners=True) is `vs_upsample2x_nhwc` (with the image-feature add of the GS head fused).
-    The 7x7 stem conv on the RGB image is `vs_conv7x7_rgb_nhwc` (window GEMM; im2col + GEMM on the f32 / split paths).
-    Channel counts that are not multiples of 64 (96, 192) are zero-padded inside the packed weights."""
+    """`.dpt` holds the parameters (reference naming: <head>.dpt.<...>); the forward drives the hand-written HIP kernels.  `_trunk`, the same
+    for both heads: every 3x3 convolution is the implicit-GEMM MFMA kernel behind `ops.conv3x3_nhwc`, its ReLUs / bias / residuals fused; every
+    1x1 convolution and both ConvTranspose2d(k == stride) are plain GEMMs -- tokens [BT, gh*gw, C] ARE an NHWC gh x gw map; bilinear x2 is
+    `ops.upsample2x_nhwc`; channel counts that are no multiple of 64 (96) are zero-padded in the packed weights.  The tail is a route of the module
+    docstring: pts3d split_packed_dot / fused16 / unfused; gs split_stream_stem / split_stem_up / split_up_packed / fused16 / unfused."""
 
     def __init__(self, net, num_channels: int, head_type: str):
         super().__init__()
@@ -141,7 +180,7 @@ class PixelwiseTaskWithDPT(nn.Module):
             P[name + ".b"] = None if conv.bias is None else conv.bias.detach().float().contiguous()
 
         ap = d.act_postprocess
-        c0, c1 = _pad_to(ap[0][0].out_channels), _pad_to(ap[1][0].out_channels)   # 96 -> 128, 192 -> 192? (192 % 64 == 0)
+        c0, c1 = _pad_to(ap[0][0].out_channels), _pad_to(ap[1][0].out_channels)   # 96 -> 128; 192 stays (a multiple of 64 already)
         lin("ap0.0", ap[0][0], n_pad=c0); convT("ap0.1", ap[0][1], k_pad=c0, co_pad=c0)
         lin("ap1.0", ap[1][0], n_pad=c1); convT("ap1.1", ap[1][1], k_pad=c1, co_pad=c1)
         lin("ap2.0", ap[2][0])
@@ -153,40 +192,48 @@ class PixelwiseTaskWithDPT(nn.Module):
             for u in ("resConfUnit1", "resConfUnit2"):
                 c3(f"rf{r}.{u}.c1", getattr(f, u).conv1); c3(f"rf{r}.{u}.c2", getattr(f, u).conv2)
             lin(f"rf{r}.out", f.out_conv)
+        c3("h0", d.head[0]); lin("h4", d.head[4])
         if self.head_type == "regression":
-            c3("h0", d.head[0]); c3("h2", d.head[2]); lin("h4", d.head[4])
-            lin("h4f", d.head[4], n_pad=4)                       # fused form: [4, 128] rows (row 3 zero), bias [4]
+            c3("h2", d.head[2]); lin("h4f", d.head[4], n_pad=4)   # fused form: [4, 128] rows (row 3 zero), bias [4]
         else:
-            c3("h0", d.head[0]); lin("h4", d.head[4])
             lin("h4f", d.head[4], n_pad=_pad_to(self.num_channels, 16))   # fused form: channels padded to a multiple of 16
         self._pk, self._pk_key = P, key
         return P
 
-    def _stem_weights(self):
-        P = self._packed()
-        if "stem.w" not in P:
-            c = self.dpt.input_merger[0]
-            P["stem.w"] = ops.pack_conv7x7_rgb_weight(c.weight, self.compute_dtype)
-            P["stem.b"] = c.bias.detach().float().contiguous()
-        return P["stem.w"], P["stem.b"]
+    # Weights that one route alone reads, made on first use per weight version (`_lazy`).  Made in _packed, "stem.e" would cost every head of
+    # every class a host synchronisation, and each class would pack what it never reads.
+    _LAZY = {
+        "h4f32.w": lambda s, P: F.pad(s.dpt.head[4].weight.detach().float().flatten(1), (0, 0, 0, 4 - s.dpt.head[4].out_channels)).contiguous(),
+        "h4f32.b": lambda s, P: F.pad(s.dpt.head[4].bias.detach().float(), (0, 4 - s.dpt.head[4].out_channels)).contiguous(),   # split dot head: f32 [4, 128], [4]
+        "stem.b": lambda s, P: s.dpt.input_merger[0].bias.detach().float().contiguous(),
+        "stem.w": lambda s, P: ops.pack_conv7x7_rgb_weight(s.dpt.input_merger[0].weight, s.compute_dtype),     # 16-bit window GEMM
+        "stem.ws7": lambda s, P: ops.pack_conv7x7_rgb_weight(s.dpt.input_merger[0].weight, "split"),            # split window GEMM
+        "stem.w32": lambda s, P: s.dpt.input_merger[0].weight.detach().float().contiguous(),                     # streaming stem: packs in the kernel ...
+        "stem.e": lambda s, P: ops.split_scale_exp(s._lazy(P, "stem.w32")),                                      # ... with this exponent (one host read)
+        "stem.wk": lambda s, P: F.pad(s.dpt.input_merger[0].weight.detach().float().flatten(1), (0, 160 - 147)).contiguous(),   # im2col stem: (c, ky, kx) rows, K 147 -> 160
+        "stem.ws": lambda s, P: ops.split_pack_weight(s._lazy(P, "stem.wk")),                                    # ... and its split-class packing
+    }
 
-    def _stem_f32(self, frames: torch.Tensor) -> torch.Tensor:
-        """7x7 stem of the reference-precision (f32) path: im2col rows (c, ky, kx order = weight.flatten(1)), K padded 147 -> 160,
-        through the f32 MFMA GEMM; a few frames at a time (65 536 x 160 floats per frame)."""
-        c = self.dpt.input_merger[0]
+    def _lazy(self, P, key):
+        if key not in P:
+            P[key] = self._LAZY[key](self, P)
+        return P[key]
+
+    def _stem(self, stem: str, frames: torch.Tensor, P) -> torch.Tensor:
+        """The 7x7 stem (dpt_gs_head.py:112-118) as a map of its own [N,H,W,Cout], bias fused; its ReLU rides on the upsample-add that reads it."""
         N, _, H, W = frames.shape
-        wk = F.pad(c.weight.detach().float().flatten(1), (0, 160 - 147)).contiguous()
-        if self.split:
-            P = self._packed()
-            if "stem.ws" not in P:
-                P["stem.ws"] = ops.split_pack_weight(wk)
-            wk = P["stem.ws"]
-        bias = c.bias.detach().float().contiguous()
+        bias = self._lazy(P, "stem.b")
+        if stem == "split7":
+            return ops.conv7x7_rgb_nhwc(ops.pad_rgb_nhwc(frames, torch.float32), self._lazy(P, "stem.ws7"), bias, H, W)
+        if stem == "window16":
+            return ops.conv7x7_rgb_nhwc(ops.pad_rgb_nhwc(frames, self.compute_dtype), self._lazy(P, "stem.w"), bias, H, W)
+        assert stem == "im2col_f32", stem
+        # reference precision: im2col rows through the f32 (or split) MFMA GEMM, 8 frames at a time (65 536 x 160 floats per frame)
+        wk = self._lazy(P, "stem.ws" if self.split else "stem.wk")
         out = torch.empty(N, H, W, wk.shape[0], dtype=torch.float32, device=frames.device)
-        step = 8
-        for i in range(0, N, step):
-            cols = F.pad(F.unfold(frames[i:i + step].float(), 7, padding=3).transpose(1, 2), (0, 160 - 147)).reshape(-1, 160).contiguous()
-            ops.gemm(cols, wk, bias, out[i:i + step].view(-1, wk.shape[0]), ops.EPI_STORE16)
+        for i in range(0, N, 8):
+            cols = F.pad(F.unfold(frames[i:i + 8].float(), 7, padding=3).transpose(1, 2), (0, 160 - 147)).reshape(-1, 160).contiguous()
+            ops.gemm(cols, wk, bias, out[i:i + 8].view(-1, wk.shape[0]), ops.EPI_STORE16)
         return out
 
     @staticmethod
@@ -218,9 +265,8 @@ class PixelwiseTaskWithDPT(nn.Module):
     def _trunk(self, tokens, gh: int, gw: int, packed_out: bool = False):
         """tokens[hook] [BT, gh*gw, C] 16-bit -> path_1 [BT, 8gh, 8gw, 256] (dpt_head.py:35-62)."""
         P = self._packed()
-        d = self.dpt
         dt = self.compute_dtype
-        t = [tokens[h] for h in d.hooks]
+        t = [tokens[h] for h in self.dpt.hooks]
         BT = t[0].shape[0]
         maps = [x.reshape(BT, gh, gw, x.shape[-1]).to(dt).contiguous() for x in t]
         # reassemble: 1x1 (+ ConvT k=s as a GEMM followed by a depth-to-space copy)
@@ -239,40 +285,23 @@ class PixelwiseTaskWithDPT(nn.Module):
         # packed_out (split class, pts3d head): path_1 only feeds a 3x3 convolution -- the bilinear kernel writes it packed (hi, lo)
         return self._fusion(P, 1, p2, l0, packed_out=packed_out), P
 
+    operand_class = property(lambda self: "split" if self.split else _CLASS_OF[self.compute_dtype])      # as the route functions name it
+
     def forward_pts3d_raw(self, tokens, gh: int, gw: int) -> torch.Tensor:
         """-> [BT,C,H,W] view (channels-last memory, pixel stride 4) of the head output in the compute dtype, BEFORE the 'exp' post-process;
         C = 3 (xyz), or 4 with the confidence channel (predict_conf: the same fused kernels, whose fourth output column was zero padding)."""
-        nc = self.num_channels
-        pk = self.split and self.dpt.head[0].out_channels == 128 and self.dpt.head[0].in_channels in (64, 128, 256)
-        x, P = self._trunk(tokens, gh, gw, packed_out=pk and (tokens[self.dpt.hooks[0]].shape[0] * 64 * gh * gw) >= 224 * 256)
+        h, nc = self.dpt.head, self.num_channels
+        route, trunk_packed = pts3d_route(self.operand_class, tokens[self.dpt.hooks[0]].shape[0], gh, gw, h[0].in_channels, h[0].out_channels, h[2].out_channels)
+        x, P = self._trunk(tokens, gh, gw, packed_out=trunk_packed)
         x = ops.conv3x3_nhwc(x, P["h0.w"], P["h0.b"])
-        npix = x.shape[0] * 4 * x.shape[1] * x.shape[2]
-        if self.split and npix % 256 == 0 and x.shape[-1] == 128 and self.dpt.head[2].out_channels == 128:
-            # round 4: the upsampled 256^2 x 128 map is written PACKED (hi, lo) by the bilinear kernel (same bytes) and the fused conv3 -> ReLU ->
-            # dot head reads it without converting (conv3x3_256x128_split_kernel<., ., A_PACKED>)
-            if "h4f32.w" not in P:
-                c4 = self.dpt.head[4]
-                P["h4f32.w"] = torch.nn.functional.pad(c4.weight.detach().float().flatten(1), (0, 0, 0, 4 - c4.out_channels)).contiguous()
-                P["h4f32.b"] = torch.nn.functional.pad(c4.bias.detach().float(), (0, 4 - c4.out_channels)).contiguous()
-            xp = ops.upsample2x_nhwc(x, packed=True)
-            y = ops.conv3x3_head1x1_nhwc(xp, P["h2.w"], P["h2.b"], P["h4f32.w"], P["h4f32.b"], nc)          # [BT,H,W,4] f32
-            return y[..., :nc].permute(0, 3, 1, 2)
-        x = ops.upsample2x_nhwc(x)
-        npix = x.shape[0] * x.shape[1] * x.shape[2]
-        if self.split and npix % 256 == 0 and x.shape[-1] == 128 and self.dpt.head[2].out_channels == 128:
-            # split operands: the same fusion in f32 (conv3 -> ReLU -> three 128-long dot products per pixel), w2 stays f32
-            if "h4f32.w" not in P:
-                c4 = self.dpt.head[4]
-                P["h4f32.w"] = torch.nn.functional.pad(c4.weight.detach().float().flatten(1), (0, 0, 0, 4 - c4.out_channels)).contiguous()
-                P["h4f32.b"] = torch.nn.functional.pad(c4.bias.detach().float(), (0, 4 - c4.out_channels)).contiguous()
-            y = ops.conv3x3_head1x1_nhwc(x, P["h2.w"], P["h2.b"], P["h4f32.w"], P["h4f32.b"], nc)          # [BT,H,W,4] f32
-            return y[..., :nc].permute(0, 3, 1, 2)
-        if self.compute_dtype != torch.float32 and npix % 256 == 0 and x.shape[-1] == 128:
-            # conv3(128->128) -> ReLU -> conv1(128->3) in one kernel: the 128-channel activation at full resolution never reaches HBM
-            y = ops.conv3x3_head1x1_nhwc(x, P["h2.w"], P["h2.b"], P["h4f.w"], P["h4f.b"], nc)          # [BT,H,W,4]
-            return y[..., :nc].permute(0, 3, 1, 2)
-        x = ops.conv3x3_nhwc(x, P["h2.w"], P["h2.b"], relu_out=True)
-        y = self._gemm1x1(x, P, "h4f")                                                               # [BT,H,W,4]: rows >= nc are zero padding
+        # every arm -> [BT,H,W,4] (columns >= nc zero padding); in the one-kernel forms the 128-channel full-resolution activation never reaches HBM
+        if route == "split_packed_dot":      # (hi, lo) pairs from the bilinear kernel (same bytes as f32): the head's main loop converts nothing
+            y = ops.conv3x3_head1x1_nhwc(ops.upsample2x_nhwc(x, packed=True), P["h2.w"], P["h2.b"], self._lazy(P, "h4f32.w"), self._lazy(P, "h4f32.b"), nc)
+        elif route == "fused16":
+            y = ops.conv3x3_head1x1_nhwc(ops.upsample2x_nhwc(x), P["h2.w"], P["h2.b"], P["h4f.w"], P["h4f.b"], nc)
+        else:
+            assert route == "unfused", route
+            y = self._gemm1x1(ops.conv3x3_nhwc(ops.upsample2x_nhwc(x), P["h2.w"], P["h2.b"], relu_out=True), P, "h4f")
         return y[..., :nc].permute(0, 3, 1, 2)
 
     def forward_pts3d(self, tokens, gh: int, gw: int) -> torch.Tensor:
@@ -289,53 +318,23 @@ class PixelwiseTaskWithDPT(nn.Module):
 
     def forward_gs(self, tokens, frames: torch.Tensor, gh: int, gw: int) -> torch.Tensor:
         """-> [BT,C,H,W] view (channels-last memory) of the raw Gaussian parameters (dpt_gs_head.py:120-157)."""
+        d, nc = self.dpt, self.num_channels
         x, P = self._trunk(tokens, gh, gw)
-        d = self.dpt
-        dt = self.compute_dtype
-        # 7x7 stem on the RGB image (dpt_gs_head.py:112-118): window GEMM on the zero-bordered NHWC frames, bias fused; its
-        # ReLU is fused into the upsample-add kernel below
-        fuse_gs = (self.split and self.num_channels <= 96 and (x.shape[0] * 4 * x.shape[1] * x.shape[2]) % 256 == 0
-                   and self.dpt.head[0].out_channels == 256 and x.shape[-1] in (32, 64, 128, 256))
-        if self.split and self.dpt.input_merger[0].out_channels % 256 == 0:
-            P = self._packed()
-            if "stem.ws7" not in P:
-                c7 = self.dpt.input_merger[0]
-                P["stem.ws7"], P["stem.b"] = ops.pack_conv7x7_rgb_weight(c7.weight, "split"), c7.bias.detach().float().contiguous()
-            H_, W_ = frames.shape[-2], frames.shape[-1]
-            if (fuse_gs and x.shape[-1] == d.input_merger[0].out_channels and x.is_contiguous()
-                    and (2 * x.shape[1], 2 * x.shape[2]) == (H_, W_)):
-                # round 4: up2(trunk) + relu(stem) leaves the STEM kernel's epilogue in the packed form -- the f32 stem map (12.9 GB written and
-                # read back per 24-scene step) and the stand-alone upsample-add launch are gone
-                if W_ % 32 == 0 and d.input_merger[0].out_channels == 256:
-                    # round 5: the streaming form (csrc/stem_stream.hip): the image as an LDS ring, taps by transpose reads, 9.4 -> see DESIGN
-                    if "stem.w32" not in P:
-                        c7 = d.input_merger[0]
-                        P["stem.w32"] = c7.weight.detach().float().contiguous()
-                        P["stem.e"] = ops.split_scale_exp(P["stem.w32"])
-                    xp = ops.stem7x7_up_split_stream(ops.pad_rgb_nhwc(frames, torch.float32), P["stem.w32"], P["stem.b"], H_, W_, x, P["stem.e"])
-                else:
-                    xp = ops.conv7x7_rgb_nhwc(ops.pad_rgb_nhwc(frames, torch.float32), P["stem.ws7"], P["stem.b"], H_, W_, up_add=x)
-                y = ops.conv3x3_head1x1_nhwc(xp, P["h0.w"], None, P["h4f.w"], P["h4f.b"], self.num_channels)   # [BT,H,W,96] f32
-                return y[..., :self.num_channels].permute(0, 3, 1, 2)
-            img = ops.conv7x7_rgb_nhwc(ops.pad_rgb_nhwc(frames, torch.float32), P["stem.ws7"], P["stem.b"], H_, W_)
-        elif dt == torch.float32:
-            img = self._stem_f32(frames)
+        H, W = frames.shape[-2], frames.shape[-1]
+        route, stem = gs_route(self.operand_class, gh, gw, H, W, nc, x.shape[-1], d.input_merger[0].out_channels, d.head[0].out_channels)
+        # conv3(256->256) -> ReLU -> conv1(256->nc) in one kernel (dpt_block.py:335-343; Dropout(0.1) is the identity at inference) -> [BT,H,W,96]
+        fused = lambda xin: ops.conv3x3_head1x1_nhwc(xin, P["h0.w"], None, P["h4f.w"], P["h4f.b"], nc)
+        if route == "split_stream_stem":     # up2(trunk) + relu(stem) leaves the stem kernel packed: no f32 stem map, no upsample-add launch
+            y = fused(ops.stem7x7_up_split_stream(ops.pad_rgb_nhwc(frames, torch.float32), self._lazy(P, "stem.w32"), self._lazy(P, "stem.b"), H, W, x,
+                                                  self._lazy(P, "stem.e")))
+        elif route == "split_stem_up":
+            y = fused(ops.conv7x7_rgb_nhwc(ops.pad_rgb_nhwc(frames, torch.float32), self._lazy(P, "stem.ws7"), self._lazy(P, "stem.b"), H, W, up_add=x))
+        elif route == "split_up_packed":
+            y = fused(ops.upsample2x_nhwc(x, add=self._stem(stem, frames, P), relu_add=True, packed=True))
+        elif route == "fused16":
+            y = fused(ops.upsample2x_nhwc(x, add=self._stem(stem, frames, P), relu_add=True))
         else:
-            P7 = self._stem_weights()
-            img = ops.conv7x7_rgb_nhwc(ops.pad_rgb_nhwc(frames, dt), P7[0], P7[1], frames.shape[-2], frames.shape[-1])
-        if fuse_gs:
-            # split operands: conv3(256->256) -> ReLU -> conv1(256->83) in one kernel, the second GEMM in four K-quarters on (hi, lo) images
-            # of the tile in LDS (P["h4f.w"] is the packed [96, 256] weight in this class).  The upsample-add kernel writes the 256 x 256 x 256
-            # operand in the packed (hi, lo) form (same bytes as f32): the convolution's main loop has no conversion left
-            x = ops.upsample2x_nhwc(x, add=img, relu_add=True, packed=True)
-            y = ops.conv3x3_head1x1_nhwc(x, P["h0.w"], None, P["h4f.w"], P["h4f.b"], self.num_channels)   # [BT,H,W,96] f32
-            return y[..., :self.num_channels].permute(0, 3, 1, 2)
-        x = ops.upsample2x_nhwc(x, add=img, relu_add=True)
-        if (dt != torch.float32 and self.num_channels <= 96 and (x.shape[0] * x.shape[1] * x.shape[2]) % 256 == 0
-                and self.dpt.head[0].out_channels == 256 and x.shape[-1] in (64, 128, 256, 512)):
-            # conv3(256->256) -> ReLU -> conv1(256->83) in one kernel (dpt_block.py:335-343; Dropout(0.1) is the identity at inference)
-            y = ops.conv3x3_head1x1_nhwc(x, P["h0.w"], None, P["h4f.w"], P["h4f.b"], self.num_channels)   # [BT,H,W,96]
-            return y[..., :self.num_channels].permute(0, 3, 1, 2)
-        x = ops.conv3x3_nhwc(x, P["h0.w"], None, relu_out=True)  # Dropout(0.1) is the identity at inference
-        y = self._gemm1x1(x, P, "h4")
-        return y.permute(0, 3, 1, 2)
+            assert route == "unfused", route
+            x = ops.upsample2x_nhwc(x, add=self._stem(stem, frames, P), relu_add=True)
+            y = self._gemm1x1(ops.conv3x3_nhwc(x, P["h0.w"], None, relu_out=True), P, "h4")
+        return y[..., :nc].permute(0, 3, 1, 2)
