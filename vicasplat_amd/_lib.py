@@ -15,6 +15,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _HEADER = os.path.join(_HERE, "..", "include", "vicasplat_hip.h")     # the one statement of every signature (parse_header)
+_DISTILL_HEADER = os.path.join(_HERE, "..", "include", "vicasplat_distill.h")   # the second public header: the vsd_ entries (csrc/distill.hip)
 _SO = os.environ.get("VICASPLAT_HIP_LIB") or os.path.join(_HERE, "libvicasplat_hip.so")   # (override: A/B runs of two builds)
 _lock = threading.Lock()
 ABI_VERSION = 10    # == vs_abi_version() of csrc/api.hip; INTEGRATION.md lists the entries of every version
@@ -63,7 +64,7 @@ def build(force: bool = False) -> str:
     src_dir = os.path.join(_HERE, "csrc")
     newest = max(os.path.getmtime(os.path.join(src_dir, f)) for f in os.listdir(src_dir)
                  if f.endswith((".hip", ".h", "Makefile")))
-    newest = max(newest, os.path.getmtime(_HEADER))
+    newest = max(newest, os.path.getmtime(_HEADER), os.path.getmtime(_DISTILL_HEADER))
     if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < newest:
         subprocess.check_call(["make", "-C", src_dir, "-j8"], stdout=subprocess.DEVNULL)
     return _SO
@@ -75,20 +76,22 @@ _C_RETURNS = {"int": C.c_int, "int64_t": C.c_int64, "const char *": C.c_char_p}
 _STRUCTS = {"VsRasterIn": VsRasterIn, "VsRasterOut": VsRasterOut, "VsRasterGrads": VsRasterGrads}
 
 
-def parse_header(text: str) -> dict:
-    """{name: (restype, [argtypes], takes_stream)} of every prototype in the text of include/vicasplat_hip.h.  The header is the one place
+def parse_header(text: str, prefix: str = "vs_") -> dict:
+    """{name: (restype, [argtypes], takes_stream)} of every prototype in the text of include/vicasplat_hip.h (or, with prefix="vsd_", of
+    include/vicasplat_distill.h: every entry of a header carries the header's prefix).  The header is the one place
     where a signature is written down; a prototype or a type outside its small vocabulary raises with the prototype's text (ctypes'
     default conversion would truncate or shift the arguments silently)."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*|^\s*#[^\n]*", "", text, flags=re.S | re.M)
     text = re.sub(r'extern\s+"C"\s*\{|\b(?:typedef\s+struct|enum)\b[^{;]*\{[^}]*\}[^;]*;|\btypedef\b[^;{]*;', "", text)
+    header = {"vs_": "vicasplat_hip.h", "vsd_": "vicasplat_distill.h"}.get(prefix, f"header of the {prefix} entries")
     sigs = {}
     for proto in (" ".join(p.split()) for p in text.split(";")):
         if proto in ("", "}"):
             continue
-        m = re.fullmatch(r"(.+?)\b(vs_\w+) ?\((.*)\)", proto)
+        m = re.fullmatch(r"(.+?)\b(%s\w+) ?\((.*)\)" % re.escape(prefix), proto)
         ret = m and m.group(1).strip()
         if not m or ret not in _C_RETURNS:
-            raise ValueError(f"vicasplat_hip.h: cannot parse the prototype `{proto}`")
+            raise ValueError(f"{header}: cannot parse the prototype `{proto}`")
         params = [] if m.group(3).strip() == "void" else [p.strip() for p in m.group(3).split(",")]
         argtypes = []
         for p in params:
@@ -98,7 +101,7 @@ def parse_header(text: str) -> dict:
             elif base in _C_TYPES:
                 argtypes.append(_C_TYPES[base])
             else:
-                raise ValueError(f"vicasplat_hip.h: unknown type `{p}` in the prototype `{proto}`")
+                raise ValueError(f"{header}: unknown type `{p}` in the prototype `{proto}`")
         sigs[m.group(2)] = (_C_RETURNS[ret], argtypes, bool(params) and params[-1].startswith("vs_stream_t "))
     return sigs
 
@@ -123,6 +126,8 @@ def _load() -> C.CDLL:
                 raise RuntimeError(f"{_SO} has ABI version {L.vs_abi_version()}, this package needs {ABI_VERSION}: rebuild it (python -c 'import __graft_entry__ as g; g.build()')")
             with open(_HEADER) as f:
                 sigs = parse_header(f.read())
+            with open(_DISTILL_HEADER) as f:
+                sigs.update(parse_header(f.read(), prefix="vsd_"))
             for name, (restype, argtypes, takes_stream) in sigs.items():
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = restype, argtypes

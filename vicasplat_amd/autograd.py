@@ -850,3 +850,24 @@ class LpipsFn(torch.autograd.Function):
         dx0 = net.features_backward(keep0, dt0_, g, normalize).to(dt0) if need0 else None
         dx1 = net.features_backward(keep1, dt1_, g, normalize).to(dt1) if need1 else None
         return dx0, dx1, None, None
+
+
+class Regr3DFn(torch.autograd.Function):
+    """The distillation point loss (src/loss/loss_conf_point.py:188-252, norm mode 'avg_dis') on the HIP kernels (ops.regr3d_forward /
+    ops.regr3d_backward): a scalar, differentiable in the predicted points and confidences.  The pseudo-GT, the quantiles and the mask
+    carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, gt1, gt2, pr1, pr2, cg1, cg2, pc1, pc2, normalize_pts):
+        loss, work = ops.regr3d_forward(gt1, gt2, pr1, pr2, cg1, cg2, pc1, pc2, normalize_pts)
+        ctx.save_for_backward(gt1, gt2, pr1, pr2, cg1, cg2, pc1, pc2, work)
+        ctx.normalize_pts = bool(normalize_pts)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        *ts, work = ctx.saved_tensors
+        d1, d2, c1, c2 = ops.regr3d_backward(*ts, ctx.normalize_pts, g, work)
+        pr1, pr2, pc1, pc2 = ts[2], ts[3], ts[6], ts[7]
+        return (None, None, d1.to(pr1.dtype), d2.to(pr2.dtype), None, None, None if c1 is None else c1.to(pc1.dtype),
+                None if c2 is None else c2.to(pc2.dtype), None)

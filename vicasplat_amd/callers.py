@@ -16,6 +16,8 @@ scripts do around the encoder/decoder:
   * `camera_loss`, `camera_dq_loss` — src/loss/loss_camera.py:30-80 (dual-quaternion algebra of src/misc/dq.py restated)
   * `LossLpips` — src/loss/loss_lpips.py:27-54 (published LPIPS-VGG algorithm; the pretrained weights must be supplied, see the class)
   * `LpipsVgg`, `compute_lpips` — lpips.LPIPS(net="vgg") and src/evaluation/metrics.py:37-44 on the HIP kernels (LossLpips(backend="hip"))
+  * `Regr3D`, `distillation_loss` — src/loss/loss_conf_point.py:188-252 and the glue of model_wrapper.py:260-299 (training stage 1: the point loss
+    against a DUSt3R / MASt3R teacher's outputs, which enter as tensors) on csrc/distill.hip; `training_step(distill=...)` applies it
   * `configure_optimizer`, `training_step` — ModelWrapper.configure_optimizers / training_step (model_wrapper.py:884-951,
     184-321): AdamW(lr, wd 0.05, betas 0.9/0.95) with the backbone-lr multiplier, encoder -> rasterizer -> MSE ->
     backward on the HIP kernels (vicasplat_amd.autograd) -> optional gradient all-reduce -> clip 0.5 -> step.
@@ -699,6 +701,82 @@ def compute_lpips(ground_truth: Tensor, predicted: Tensor, net: LpipsVgg) -> Ten
     return net(ground_truth, predicted, normalize=True)[:, 0, 0, 0].to(predicted.dtype)
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# distillation point loss -- src/loss/loss_conf_point.py:188-252 (Regr3D) as ModelWrapper.training_step applies it
+# (model_wrapper.py:248-301).  The teacher network is out of scope: its points and confidences enter as tensors.
+# ---------------------------------------------------------------------------------------------------------------------------
+class Regr3D(torch.nn.Module):
+    """The reference's Regr3D: pixels whose pseudo-GT distance lies within the [1 %, 99 %] quantiles of their view (per batch element,
+    torch.quantile's linear interpolation) are valid; loss = mean over valid of gt_conf |gt - pr|, per view, summed, plus -- when both
+    predicted confidences are given -- mean |pr_conf - gt_conf| per view.  normalize_pts divides prediction and pseudo-GT each by their own
+    average valid distance over both views (normalize_pointcloud 'avg_dis', ptc_geometry.py:270-328).  forward has the reference's signature
+    and order; `dist_clip` and `disable_view1` are accepted and, as there, never read, and so are `alpha` and `gt_scale`.
+    backend="hip": csrc/distill.hip (selection instead of sorting, two streaming passes, one backward pass; HIP device tensors, no
+    fallback).  backend="torch": the plain restatement in PyTorch (CPU tests, the benchmark's baseline)."""
+
+    def __init__(self, norm_mode: str = "avg_dis", alpha: float = 0.2, gt_scale: bool = False, backend: str = "hip"):
+        super().__init__()
+        if norm_mode != "avg_dis":
+            raise NotImplementedError(f"Regr3D: only norm_mode='avg_dis' (every released configuration) is implemented, got {norm_mode!r}")
+        if backend not in ("torch", "hip"):
+            raise ValueError(f'Regr3D: backend must be "torch" or "hip", got {backend!r}')
+        self.norm_mode, self.alpha, self.gt_scale, self.backend = norm_mode, alpha, gt_scale, backend
+
+    @staticmethod
+    def _normalize(p1: Tensor, p2: Tensor, valid1: Tensor, valid2: Tensor):
+        B = p1.shape[0]
+        zero = lambda p, valid: torch.where(valid[..., None], p, torch.zeros_like(p))      # invalid_to_zeros: assigned, not multiplied (a non-finite point outside the mask is ignored)
+        dis = torch.cat([zero(p1, valid1).reshape(B, -1, 3), zero(p2, valid2).reshape(B, -1, 3)], dim=1).norm(dim=-1)
+        nnz = valid1.reshape(B, -1).sum(dim=1) + valid2.reshape(B, -1).sum(dim=1)
+        f = (dis.sum(dim=1) / (nnz + 1e-8)).clip(min=1e-8).view(B, 1, 1, 1)
+        return p1 / f, p2 / f
+
+    def forward(self, gt_pts1, gt_pts2, pr_pts1, pr_pts2, gt_conf1, gt_conf2, pr_conf1=None, pr_conf2=None, dist_clip=None,
+                normalize_pts=False, disable_view1=False):
+        if self.backend == "hip":
+            from . import autograd as A
+            if pr_conf1 is None or pr_conf2 is None:
+                pr_conf1 = pr_conf2 = None
+            return A.Regr3DFn.apply(gt_pts1, gt_pts2, pr_pts1, pr_pts2, gt_conf1, gt_conf2, pr_conf1, pr_conf2, bool(normalize_pts))
+        dis1, dis2 = gt_pts1.norm(dim=-1), gt_pts2.norm(dim=-1)
+        q = torch.tensor([0.01, 0.99], dtype=dis1.dtype, device=dis1.device)
+        q1, q2 = torch.quantile(dis1.flatten(1), q, dim=1), torch.quantile(dis2.flatten(1), q, dim=1)
+        valid1 = (dis1 >= q1[0].view(-1, 1, 1)) & (dis1 <= q1[1].view(-1, 1, 1))
+        valid2 = (dis2 >= q2[0].view(-1, 1, 1)) & (dis2 <= q2[1].view(-1, 1, 1))
+        if normalize_pts:
+            pr_pts1, pr_pts2 = self._normalize(pr_pts1, pr_pts2, valid1, valid2)
+            gt_pts1, gt_pts2 = self._normalize(gt_pts1, gt_pts2, valid1, valid2)
+        l1 = gt_conf1 * torch.norm(gt_pts1 - pr_pts1, dim=-1)
+        l2 = gt_conf2 * torch.norm(gt_pts2 - pr_pts2, dim=-1)
+        loss = l1[valid1].mean() + l2[valid2].mean()
+        if pr_conf1 is not None and pr_conf2 is not None:
+            loss = loss + (pr_conf1 - gt_conf1).abs().mean() + (pr_conf2 - gt_conf2).abs().mean()
+        return loss
+
+
+def distillation_loss(out: dict, pseudo_gt1: dict, pseudo_gt2: dict, frame_idx: Tensor, segment_idx: Tensor, context_extrinsics: Tensor,
+                      weight: float = 1.0, loss_fn: Regr3D | None = None) -> Tensor:
+    """The distillation term of ModelWrapper.training_step (model_wrapper.py:260-299) from the teacher's outputs.
+    out: the encoder's outputs (`gaussian_centers` [B,V,H,W,3], `confidence` [B,V,H,W] or None); pseudo_gt1 / pseudo_gt2: the teacher's
+    {"pts3d" [B,H,W,3], "conf" [B,H,W]} for the two anchor frames, in the first anchor's camera space; frame_idx [B,2] (int64): the
+    anchors' frame numbers; segment_idx [B,2] (int64): the views whose predictions they are compared with; context_extrinsics [B,V,4,4].
+    The teacher's points are moved into the first video frame's space by the first anchor's extrinsics; the points are normalised when
+    the video has more than two views; the result is multiplied by `weight` (train.distill_weight).  `loss_fn`: a Regr3D (default: the
+    HIP backend)."""
+    loss_fn = Regr3D() if loss_fn is None else loss_fn
+    E = torch.gather(context_extrinsics.float(), 1, frame_idx[:, :1, None, None].expand(-1, 1, 4, 4)).squeeze(1)
+    R, t = E[:, :3, :3], E[:, None, None, :3, 3]
+    gt1 = torch.einsum("bij,bhwj->bhwi", R, pseudo_gt1["pts3d"].float()) + t
+    gt2 = torch.einsum("bij,bhwj->bhwi", R, pseudo_gt2["pts3d"].float()) + t
+    xyz, conf = out["gaussian_centers"], out.get("confidence")
+    pr1, pr2 = torch.gather(xyz, 1, segment_idx[..., None, None, None].expand(-1, -1, *xyz.shape[-3:])).unbind(1)
+    pc1 = pc2 = None
+    if conf is not None:
+        pc1, pc2 = torch.gather(conf, 1, segment_idx[..., None, None].expand(-1, -1, *conf.shape[-2:])).unbind(1)
+    return loss_fn(gt1, gt2, pr1, pr2, pseudo_gt1["conf"].float(), pseudo_gt2["conf"].float(), pc1, pc2,
+                   normalize_pts=xyz.shape[1] > 2) * weight
+
+
 class LossScaler:
     """Dynamic loss scale for the 16-bit activation gradients (what torch.amp.GradScaler does for f16): halve on a non-finite
     gradient norm (that step is skipped), double after `growth_interval` clean steps."""
@@ -718,7 +796,8 @@ class LossScaler:
 
 def training_step(encoder, decoder, batch: dict, optimizer, *, scheduler=None, compute_dtype=torch.float16,
                   loss_scale: float | LossScaler | None = None, clip: float = 0.5, mse_weight: float = 1.0, camera_weight: float = 0.0,
-                  extra_losses=(), allreduce: bool = False, reducer=None, global_step: int = 0, forward_fn=None) -> dict:
+                  extra_losses=(), allreduce: bool = False, reducer=None, global_step: int = 0, forward_fn=None,
+                  distill: dict | None = None) -> dict:
     """One optimisation step of the reference's objective (training_step, model_wrapper.py:184-321): MSE (loss_mse.py) + camera
     dual-quaternion loss (loss_camera.py, `camera_weight` > 0 and batch["context"]["extrinsics"] present) + `extra_losses`
     (callables (render, batch, out) -> scalar; the reference's LPIPS term needs VGG weights that are not available offline and plugs
@@ -734,7 +813,16 @@ def training_step(encoder, decoder, batch: dict, optimizer, *, scheduler=None, c
     allreduce=True (bucketed all-reduce after backward).  The skip decision of an overflowed step is taken from the norm of the
     REDUCED gradients, so every rank takes the same decision (an inf / nan on one rank reaches all of them through the sum).
     `forward_fn(encoder, image, intrinsics, compute_dtype, global_step=) -> dict` replaces the HIP training forward (tests drive the
-    step's control flow -- loss scaling, gradient exchange, clipping, skipping -- with a toy encoder / decoder on CPU)."""
+    step's control flow -- loss scaling, gradient exchange, clipping, skipping -- with a toy encoder / decoder on CPU).
+    `distill`: the distillation stage (model_wrapper.py:248-301) -- a dict with the arguments of `distillation_loss` (pseudo_gt1, pseudo_gt2,
+    frame_idx, segment_idx; optional weight, loss_fn; the extrinsics are the context's) and `only`.  The term enters the result as
+    `loss_distill`.  With `only` (distill_only, stage 1 of the recipe) the forward runs with distill=True, nothing is rendered, only the
+    camera and distillation terms are summed and the result has no `psnr` (the reference's distill_only keeps the camera term alone of
+    its losses: `extra_losses` have no render to work on there and passing any raises); without it the term is added to the usual
+    objective."""
+    only = distill is not None and bool(distill.get("only", False))
+    if only and len(extra_losses):
+        raise ValueError("training_step: distill['only'] renders nothing, so `extra_losses` cannot be applied; pass none")
     if forward_fn is None:
         from .model.encoder.train_forward import forward_train as forward_fn
     ctx, tgt = batch["context"], batch["target"]
@@ -754,17 +842,24 @@ def training_step(encoder, decoder, batch: dict, optimizer, *, scheduler=None, c
         reducer.zero_grad()
     else:
         optimizer.zero_grad(set_to_none=True)
-    out = forward_fn(encoder, ctx["image"], ctx["intrinsics"], compute_dtype, global_step=global_step)
-    g = out["gaussians"]
-    gs = Gaussians(g["means"].flatten(1, 3), g["covariances"].flatten(1, 3), g["harmonics"].flatten(1, 3), g["opacities"].flatten(1))
-    h, w = tgt["image"].shape[-2:]
-    render = decoder.forward(gs, tgt["extrinsics"], tgt["intrinsics"], tgt["near"], tgt["far"], (h, w))
-    parts = dict(mse=mse_loss(render.color, tgt["image"], mse_weight))
+    if only:
+        out = forward_fn(encoder, ctx["image"], ctx["intrinsics"], compute_dtype, global_step=global_step, distill=True)
+        render, parts = None, {}
+    else:
+        out = forward_fn(encoder, ctx["image"], ctx["intrinsics"], compute_dtype, global_step=global_step)
+        g = out["gaussians"]
+        gs = Gaussians(g["means"].flatten(1, 3), g["covariances"].flatten(1, 3), g["harmonics"].flatten(1, 3), g["opacities"].flatten(1))
+        h, w = tgt["image"].shape[-2:]
+        render = decoder.forward(gs, tgt["extrinsics"], tgt["intrinsics"], tgt["near"], tgt["far"], (h, w))
+        parts = dict(mse=mse_loss(render.color, tgt["image"], mse_weight))
     if camera_weight > 0 and "extrinsics" in ctx:
         parts["camera"] = camera_loss(out["pred_extrins"], ctx["extrinsics"].float(), camera_weight, pred_intrins=out.get("pred_intrins"),
                                       context_intrinsics=ctx["intrinsics"])
     for i, fn in enumerate(extra_losses):
         parts[getattr(fn, "__name__", f"extra{i}")] = fn(render, batch, out)
+    if distill is not None:
+        parts["distill"] = distillation_loss(out, distill["pseudo_gt1"], distill["pseudo_gt2"], distill["frame_idx"], distill["segment_idx"],
+                                             ctx["extrinsics"], distill.get("weight", 1.0), distill.get("loss_fn"))
     loss = sum(parts.values())
     (loss * scale).backward()
     params = [p for p in encoder.parameters() if p.requires_grad]
@@ -787,7 +882,10 @@ def training_step(encoder, decoder, batch: dict, optimizer, *, scheduler=None, c
         optimizer.zero_grad(set_to_none=True)
     if isinstance(loss_scale, LossScaler):
         loss_scale.update(finite)
-    with torch.no_grad():
-        psnr = compute_psnr(tgt["image"].flatten(0, 1), render.color.detach().flatten(0, 1)).mean()
-    return dict(loss=loss.detach(), psnr=psnr, grad_norm=gnorm, skipped=not finite, pred_extrins=out["pred_extrins"].detach(),
-                loss_scale=scale, **{"loss_" + k: v.detach() for k, v in parts.items()})
+    res = dict(loss=loss.detach())
+    if not only:
+        with torch.no_grad():
+            res["psnr"] = compute_psnr(tgt["image"].flatten(0, 1), render.color.detach().flatten(0, 1)).mean()
+    res.update(grad_norm=gnorm, skipped=not finite, pred_extrins=out["pred_extrins"].detach(), loss_scale=scale,
+               **{"loss_" + k: v.detach() for k, v in parts.items()})
+    return res

@@ -1425,3 +1425,51 @@ def lpips_head_backward(taps0, taps1, lins, g: torch.Tensor, need0: bool, need1:
     L.call("vs_lpips_head_backward", dev, _ptr_array(taps0), _ptr_array(taps1), _ptr_array(lins), L.ptr(g), N, H, W, lpips_scale_log2(H, W),
            None if d0 is None else _ptr_array(d0), None if d1 is None else _ptr_array(d1))
     return d0, d1
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# distillation point loss (csrc/distill.hip, include/vicasplat_distill.h)
+# ---------------------------------------------------------------------------------------------------------------------------
+def _regr3d_args(gt1, gt2, pr1, pr2, cg1, cg2, pc1, pc2):
+    if pc1 is None or pc2 is None:       # the reference adds the confidence term only when both are given
+        pc1 = pc2 = None
+    dev = L.require_device(gt1, gt2, pr1, pr2, cg1, cg2, pc1, pc2)
+    if gt1.dim() != 4 or gt1.shape[-1] != 3 or gt1.numel() == 0:
+        raise ValueError(f"Regr3D takes points [B, H, W, 3], got {tuple(gt1.shape)}")
+    B, H, W, _ = gt1.shape
+    for t, shape in ((gt2, (B, H, W, 3)), (pr1, (B, H, W, 3)), (pr2, (B, H, W, 3)), (cg1, (B, H, W)), (cg2, (B, H, W)), (pc1, (B, H, W)), (pc2, (B, H, W))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"Regr3D: expected a tensor of shape {shape}, got {tuple(t.shape)}")
+    ts = [None if t is None else t.detach().float().contiguous() for t in (gt1, gt2, pr1, pr2, cg1, cg2, pc1, pc2)]
+    return dev, ts, (B, H, W)
+
+
+def regr3d_forward(gt1, gt2, pr1, pr2, cg1, cg2, pc1=None, pc2=None, normalize_pts: bool = False):
+    """(loss [] f32, workspace) of the distillation point loss (vsd_regr3d_forward); the workspace goes to regr3d_backward with the same
+    inputs.  Waits for the stream once: a NaN among the pseudo-GT points raises RuntimeError."""
+    dev, ts, (B, H, W) = _regr3d_args(gt1, gt2, pr1, pr2, cg1, cg2, pc1, pc2)
+    nbytes = L.call("vsd_regr3d_workspace_bytes", dev, B, H, W)
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    L.call("vsd_regr3d_forward", dev, *[L.ptr(t) for t in ts], B, H, W, int(bool(normalize_pts)), L.ptr(work), nbytes, L.ptr(loss))
+    return loss, work
+
+
+def regr3d_backward(gt1, gt2, pr1, pr2, cg1, cg2, pc1, pc2, normalize_pts: bool, grad_loss: torch.Tensor, work: torch.Tensor):
+    """(d_pr_pts1, d_pr_pts2, d_pr_conf1, d_pr_conf2) of grad_loss * loss (vsd_regr3d_backward); the last two are None without both pr_conf."""
+    dev, ts, (B, H, W) = _regr3d_args(gt1, gt2, pr1, pr2, cg1, cg2, pc1, pc2)
+    g = grad_loss.detach().reshape(1).float().contiguous()
+    d1, d2 = torch.empty(B, H, W, 3, dtype=torch.float32, device=dev), torch.empty(B, H, W, 3, dtype=torch.float32, device=dev)
+    has_conf = ts[6] is not None
+    c1 = torch.empty(B, H, W, dtype=torch.float32, device=dev) if has_conf else None
+    c2 = torch.empty(B, H, W, dtype=torch.float32, device=dev) if has_conf else None
+    L.call("vsd_regr3d_backward", dev, *[L.ptr(t) for t in ts], B, H, W, int(bool(normalize_pts)), L.ptr(g), L.ptr(work), work.numel(),
+           L.ptr(d1), L.ptr(d2), L.ptr(c1), L.ptr(c2))
+    return d1, d2, c1, c2
+
+
+def regr3d_workspace_view(work: torch.Tensor, B: int) -> dict:
+    """What the forward left in its workspace, for tests and diagnostics: thresholds [2, B, 2] (view, element, (q01, q99)), the counts of
+    valid pixels per view over the batch, the factors of prediction and pseudo-GT [B]."""
+    w = work.view(torch.float32)
+    return dict(thresholds=w[8:8 + 4 * B].view(2, B, 2), counts=w[1:3], factor_pr=w[8 + 4 * B:8 + 5 * B], factor_gt=w[8 + 5 * B:8 + 6 * B])
