@@ -871,3 +871,25 @@ class Regr3DFn(torch.autograd.Function):
         pr1, pr2, pc1, pc2 = ts[2], ts[3], ts[6], ts[7]
         return (None, None, d1.to(pr1.dtype), d2.to(pr2.dtype), None, None, None if c1 is None else c1.to(pc1.dtype),
                 None if c2 is None else c2.to(pc2.dtype), None)
+
+
+class DepthSmoothFn(torch.autograd.Function):
+    """The depth-smoothness loss (src/loss/loss_depth.py:34-60) on the HIP kernels (ops.depth_smooth_forward / ops.depth_smooth_backward): a
+    scalar, differentiable in depth [N, H, W] only; near, far and the image carry no gradient.  The forward writes the gradient for an
+    upstream factor of 1 in the pass that forms the loss (when depth needs one); the backward scales it."""
+
+    @staticmethod
+    def forward(ctx, depth, near, far, image, sigma_image, use_second_derivative, weight):
+        loss, unit = ops.depth_smooth_forward(depth, near, far, image, sigma_image, use_second_derivative, weight,
+                                              need_grad=ctx.needs_input_grad[0])
+        if unit is not None:
+            ctx.save_for_backward(unit)
+        ctx.depth_dtype = depth.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.saved_tensors:
+            return None, None, None, None, None, None, None
+        (unit,) = ctx.saved_tensors
+        return ops.depth_smooth_backward(unit, g).to(ctx.depth_dtype), None, None, None, None, None, None

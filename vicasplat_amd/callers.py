@@ -18,6 +18,8 @@ scripts do around the encoder/decoder:
   * `LpipsVgg`, `compute_lpips` — lpips.LPIPS(net="vgg") and src/evaluation/metrics.py:37-44 on the HIP kernels (LossLpips(backend="hip"))
   * `Regr3D`, `distillation_loss` — src/loss/loss_conf_point.py:188-252 and the glue of model_wrapper.py:260-299 (training stage 1: the point loss
     against a DUSt3R / MASt3R teacher's outputs, which enter as tensors) on csrc/distill.hip; `training_step(distill=...)` applies it
+  * `LossDepth`, `depth_smoothness_loss` — src/loss/loss_depth.py:26-60 (edge-aware first / second differences of the rendered depth between
+    log(near) and log(far)) on csrc/depth_loss.hip; plugs into `training_step(extra_losses=[...])` and drives the rasterizer's dL_ddepth
   * `configure_optimizer`, `training_step` — ModelWrapper.configure_optimizers / training_step (model_wrapper.py:884-951,
     184-321): AdamW(lr, wd 0.05, betas 0.9/0.95) with the backbone-lr multiplier, encoder -> rasterizer -> MSE ->
     backward on the HIP kernels (vicasplat_amd.autograd) -> optional gradient all-reduce -> clip 0.5 -> step.
@@ -775,6 +777,67 @@ def distillation_loss(out: dict, pseudo_gt1: dict, pseudo_gt2: dict, frame_idx: 
         pc1, pc2 = torch.gather(conf, 1, segment_idx[..., None, None].expand(-1, -1, *conf.shape[-2:])).unbind(1)
     return loss_fn(gt1, gt2, pr1, pr2, pseudo_gt1["conf"].float(), pseudo_gt2["conf"].float(), pc1, pc2,
                    normalize_pts=xyz.shape[1] > 2) * weight
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# depth-smoothness loss -- src/loss/loss_depth.py:26-60 (LossDepth, config/loss/depth.yaml)
+# ---------------------------------------------------------------------------------------------------------------------------
+def depth_smoothness_loss(depth: Tensor, near: Tensor, far: Tensor, image: Tensor | None = None, weight: float = 1.0,
+                          sigma_image: float | None = None, use_second_derivative: bool = False, backend: str = "hip") -> Tensor:
+    """LossDepth.forward on tensors: depth [..., H, W] with near and far [...] (one pair per view) and, for the bilateral weights
+    (sigma_image not None), the target colours image [..., 3, H, W].  d = (depth clamped to [log near, log far] - log near) / (log far -
+    log near) -- the minimum first, the log on near and far only, as the reference writes it --; first or second differences of d along W
+    and along H, each times exp(-sigma_image * max over the channels of the SIGNED colour difference) (second: the larger of the two
+    neighbouring maxima); weight * (mean |dx| + mean |dy|), the means over all views at once.  Differentiable in depth only.
+    backend="hip": csrc/depth_loss.hip (one stencil pass that also writes the gradient; HIP device tensors, no fallback; H or W too small
+    for a non-empty difference raises ValueError).  backend="torch": the plain restatement (CPU tests, the benchmark's baseline)."""
+    if backend not in ("torch", "hip"):
+        raise ValueError(f'depth_smoothness_loss: backend must be "torch" or "hip", got {backend!r}')
+    if sigma_image is not None and image is None:
+        raise ValueError("depth_smoothness_loss: sigma_image is given, so the target image is needed")
+    if backend == "hip":
+        from . import autograd as A
+        H, W = depth.shape[-2:]
+        return A.DepthSmoothFn.apply(depth.reshape(-1, H, W), near.reshape(-1), far.reshape(-1),
+                                     None if sigma_image is None else image.reshape(-1, 3, H, W), sigma_image, bool(use_second_derivative),
+                                     float(weight))
+    ln, lf = near[..., None, None].log(), far[..., None, None].log()
+    d = depth.minimum(lf).maximum(ln)
+    d = (d - ln) / (lf - ln)
+    dx, dy = d.diff(dim=-1), d.diff(dim=-2)
+    if use_second_derivative:
+        dx, dy = dx.diff(dim=-1), dy.diff(dim=-2)
+    if sigma_image is not None:
+        cx, cy = image.diff(dim=-1).amax(dim=-3), image.diff(dim=-2).amax(dim=-3)
+        if use_second_derivative:
+            cx = cx[..., :, 1:].maximum(cx[..., :, :-1])
+            cy = cy[..., 1:, :].maximum(cy[..., :-1, :])
+        dx = dx * torch.exp(-cx * sigma_image)
+        dy = dy * torch.exp(-cy * sigma_image)
+    return weight * (dx.abs().mean() + dy.abs().mean())
+
+
+class LossDepth(torch.nn.Module):
+    """The reference's LossDepth with its configuration (weight, sigma_image, use_second_derivative: config/loss/depth.yaml has 0.25, null,
+    false) and its forward(prediction, batch, gaussians, global_step): reads prediction.depth [B, V, H, W] and batch["target"]["near" |
+    "far"] [B, V] (and ["image"] [B, V, 3, H, W] when sigma_image is set).  `__name__` is the reference's loss name, so an instance in
+    `training_step(extra_losses=[...])` is called as (render, batch, out) and reported as `loss_depth`; its gradient reaches the
+    rasterizer as dL_ddepth.  The reference's decoder ignores depth_mode and so renders plain depth while only near and far are
+    logged; that is kept.  backend: see depth_smoothness_loss."""
+    __name__ = "depth"
+
+    def __init__(self, weight: float = 0.25, sigma_image: float | None = None, use_second_derivative: bool = False, backend: str = "hip"):
+        super().__init__()
+        if backend not in ("torch", "hip"):
+            raise ValueError(f'LossDepth: backend must be "torch" or "hip", got {backend!r}')
+        self.weight, self.sigma_image, self.use_second_derivative, self.backend = weight, sigma_image, use_second_derivative, backend
+
+    def forward(self, prediction, batch, gaussians=None, global_step: int = 0) -> Tensor:
+        if getattr(prediction, "depth", None) is None:
+            raise ValueError("LossDepth needs a rendered depth (prediction.depth [B, V, H, W])")
+        tgt = batch["target"]
+        return depth_smoothness_loss(prediction.depth, tgt["near"], tgt["far"], tgt["image"] if self.sigma_image is not None else None,
+                                     self.weight, self.sigma_image, self.use_second_derivative, self.backend)
 
 
 class LossScaler:

@@ -1473,3 +1473,65 @@ def regr3d_workspace_view(work: torch.Tensor, B: int) -> dict:
     valid pixels per view over the batch, the factors of prediction and pseudo-GT [B]."""
     w = work.view(torch.float32)
     return dict(thresholds=w[8:8 + 4 * B].view(2, B, 2), counts=w[1:3], factor_pr=w[8 + 4 * B:8 + 5 * B], factor_gt=w[8 + 5 * B:8 + 6 * B])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# depth-smoothness loss (csrc/depth_loss.hip, include/vicasplat_loss.h)
+# ---------------------------------------------------------------------------------------------------------------------------
+# One workgroup of the tile kernel covers a band of rows times a chunk of columns of one view.  Twins of kBandRows / kChunkCols in
+# csrc/depth_loss.hip: change them together (tests/test_depth_loss_gpu.py takes its tile-edge shapes from here).
+DEPTH_SMOOTH_BAND_ROWS = 16
+DEPTH_SMOOTH_CHUNK_COLS = 64
+
+
+def _depth_smooth_args(depth, near, far, image, sigma_image, use_second_derivative):
+    if sigma_image is None:
+        image = None           # the reference reads the colours only for the bilateral weights
+    elif image is None:
+        raise ValueError("depth smoothness: sigma_image is given, so the target image [N, 3, H, W] is needed")
+    dev = L.require_device(depth, near, far, image)
+    if depth.dim() != 3 or depth.numel() == 0:
+        raise ValueError(f"depth smoothness takes depth [N, H, W], got {tuple(depth.shape)}")
+    N, H, W = depth.shape
+    for name, t, shape in (("near", near, (N,)), ("far", far, (N,)), ("image", image, (N, 3, H, W))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"depth smoothness: expected {name} of shape {shape}, got {tuple(t.shape)}")
+    for name, t in (("depth", depth), ("near", near), ("far", far), ("image", image)):
+        if t is not None and not t.is_floating_point():
+            raise ValueError(f"depth smoothness: {name} must be a floating-point tensor, got {t.dtype}")
+    need = 3 if use_second_derivative else 2
+    if H < need or W < need:
+        raise ValueError(f"depth smoothness: {H} x {W} is too small, a {'second' if use_second_derivative else 'first'} difference needs at "
+                         f"least {need} rows and columns (torch returns NaN from the empty mean)")
+    ts = [None if t is None else t.detach().float().contiguous() for t in (depth, near, far, image)]
+    return dev, ts, (N, H, W)
+
+
+def depth_smooth_forward(depth, near, far, image=None, sigma_image=None, use_second_derivative: bool = False, weight: float = 1.0,
+                         need_grad: bool = True):
+    """(loss [] f32, d_depth_unit [N, H, W] f32 or None) of the depth-smoothness loss (vsl_depth_smooth_forward): depth [N, H, W], near and
+    far [N], image [N, 3, H, W] (read only when sigma_image is not None).  d_depth_unit is d loss / d depth for an upstream gradient of 1,
+    written by the same pass (need_grad); depth_smooth_backward scales it.  No host synchronisation."""
+    dev, ts, (N, H, W) = _depth_smooth_args(depth, near, far, image, sigma_image, use_second_derivative)
+    nbytes = L.call("vsl_depth_smooth_workspace_bytes", dev, N, H, W)
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    unit = torch.empty((N, H, W), dtype=torch.float32, device=dev) if need_grad else None
+    L.call("vsl_depth_smooth_forward", dev, *[L.ptr(t) for t in ts], N, H, W, 0.0 if sigma_image is None else float(sigma_image),
+           int(bool(use_second_derivative)), float(weight), L.ptr(work), nbytes, L.ptr(loss), L.ptr(unit))
+    return loss, unit
+
+
+def depth_smooth_backward(d_depth_unit: torch.Tensor, grad_loss: torch.Tensor) -> torch.Tensor:
+    """grad_loss * d_depth_unit (vsl_depth_smooth_backward): the gradient of the depth-smoothness loss with respect to depth [N, H, W]."""
+    dev = L.require_device(d_depth_unit, grad_loss)
+    if d_depth_unit.dim() != 3 or d_depth_unit.dtype != torch.float32 or not d_depth_unit.is_contiguous() or d_depth_unit.numel() == 0:
+        raise ValueError(f"depth smoothness backward takes the contiguous f32 [N, H, W] image of the forward, got {tuple(d_depth_unit.shape)} "
+                         f"{d_depth_unit.dtype}")
+    if grad_loss.numel() != 1:
+        raise ValueError(f"depth smoothness backward: the loss is a scalar, got an upstream gradient of shape {tuple(grad_loss.shape)}")
+    N, H, W = d_depth_unit.shape
+    g = grad_loss.detach().reshape(1).float().contiguous()
+    out = torch.empty_like(d_depth_unit)
+    L.call("vsl_depth_smooth_backward", dev, L.ptr(d_depth_unit), L.ptr(g), N, H, W, L.ptr(out))
+    return out
