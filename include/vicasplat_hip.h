@@ -222,7 +222,8 @@ int vs_layernorm_mod(const float *x, int64_t ldx, const float *w, const float *b
  * ReLU -> Linear, vicasplat.py:118-138): out[m,n] = sum_k act(x[m,k]) w[n,k] + bias[n], relu_in 0 | 1; all f32, strides in elements. */
 int vs_linear_f32(const float *x, int64_t ldx, const float *w, int64_t ldw, const float *bias, float *out, int64_t ldo, int32_t M, int32_t N,
                   int32_t K, int32_t relu_in, vs_stream_t stream);
-/* out[i] = silu(x[i]), x f32 -> out_dtype 0 f32 / 1 f16 / 2 bf16 (the SiLU in front of the AdaLN projections, backbone_vica.py:210-212); n % 4 == 0 */
+/* out[i] = silu(x[i]), x f32 -> out_dtype 0 f32 / 1 f16 / 2 bf16 (the SiLU in front of the AdaLN projections, backbone_vica.py:210-212); n % 4 == 0,
+ * x 16-byte aligned, out 16-byte (f32) / 8-byte (16-bit) aligned */
 int vs_silu_cast(const float *x, void *out, int64_t n, int32_t out_dtype, vs_stream_t stream);
 
 /* out = epilogue(A[M,K] * W[N,K]^T + bias).  epilogue: 0 store 16-bit, 1 exact-erf GELU then store 16-bit,
@@ -244,7 +245,8 @@ int vs_gemm_qkv_rope(const void *A, const void *W, const float *bias, void *out,
                      float theta1d, vs_stream_t stream);
 
 /* In-place RoPE on the q (column 0) and k (column k_col) blocks of a packed projection buffer [rows, ld], H heads of
- * 64.  pos int32 [rows,2] (y,x) or (t,-); kind uint8 [rows] (0 = 2-D, 1 = temporal 1-D interleaved, 2 = none) or NULL. */
+ * 64 (k_col >= 64 H, ld >= k_col + 64 H).  pos int32 [rows,2] (y,x) or (t,-); kind uint8 [rows] (0 = 2-D, 1 = temporal 1-D interleaved,
+ * 2 = none) or NULL. */
 int vs_rope_qk(void *buf, int64_t ld, int32_t rows, int32_t H, int32_t k_col, const int32_t *pos, const uint8_t *kind,
                float base2d, float theta1d, int32_t dtype, vs_stream_t stream);
 /* Same with a direction: dir = +1 forward, -1 the inverse rotation (= the backward pass of the embedding on dq, dk). */

@@ -309,6 +309,7 @@ extern "C" int vs_silu_cast(const float *x, void *out, int64_t n, int32_t out_dt
     hipStream_t stream = (hipStream_t)stream_;
     VS_CHECK(x && out, "vs_silu_cast: null pointer");
     VS_CHECK(n % 4 == 0 && out_dtype >= 0 && out_dtype <= 2, "vs_silu_cast: n must be a multiple of 4, out_dtype 0 f32 / 1 f16 / 2 bf16");
+    VS_CHECK(((uintptr_t)x & 15) == 0 && ((uintptr_t)out & (out_dtype == 0 ? 15 : 7)) == 0, "vs_silu_cast: x must be 16-byte aligned, out 16-byte (f32) / 8-byte (16-bit)");
     if (n <= 0) return 0;
     dim3 grid((unsigned)vs::cdiv64(n / 4, 256)), block(256);
     switch (out_dtype) {
@@ -350,6 +351,7 @@ extern "C" int vs_rope_qk_dir(void *buf, int64_t ld, int32_t rows, int32_t H, in
     VS_CHECK(buf && pos, "vs_rope_qk: null pointer");
     VS_CHECK(dtype >= 0 && dtype <= 2, "vs_rope_qk: dtype must be 0 (f32), 1 (f16) or 2 (bf16)");
     VS_CHECK(dir == 1.0f || dir == -1.0f, "vs_rope_qk_dir: dir must be +1 (forward) or -1 (inverse / backward)");
+    VS_CHECK(H <= 0 || (k_col >= 64 * H && ld >= (int64_t)k_col + 64 * H), "vs_rope_qk: q [0, 64 H) and k [k_col, k_col + 64 H) must be disjoint and inside a row (H=%d k_col=%d ld=%lld)", H, k_col, (long long)ld);
     if (rows <= 0 || H <= 0) return 0;
     dim3 grid(vs::cdiv(rows, 4)), block(256);
     if (dtype == 2) hipLaunchKernelGGL(rope_qk_kernel<2>, grid, block, 0, stream, (unsigned short *)buf, ld, rows, H, k_col, pos, kind, base2d, theta1d, dir);

@@ -726,7 +726,7 @@ def gated_resid_backward(dout: torch.Tensor, y: torch.Tensor, gate: Optional[tor
 
 
 def gelu16(z: torch.Tensor) -> torch.Tensor:
-    """gelu_erf(z) on a contiguous 16-bit tensor (numel % 8 == 0)."""
+    """gelu_erf(z) on a contiguous f16 / bf16 tensor (numel % 8 == 0) or f32 tensor (numel % 4 == 0), in the dtype of z."""
     dev = L.require_device(z)
     assert z.is_contiguous() and z.dtype in (torch.float16, torch.bfloat16, torch.float32)
     out = torch.empty_like(z)
@@ -738,7 +738,7 @@ def gelu16(z: torch.Tensor) -> torch.Tensor:
 
 
 def gelu_backward(dy: torch.Tensor, z: torch.Tensor) -> torch.Tensor:
-    """dz = dy * gelu_erf'(z); dy, z contiguous 16-bit of the same shape (numel % 8 == 0)."""
+    """dz = dy * gelu_erf'(z); dy, z contiguous of the same shape and dtype: f16 / bf16 (numel % 8 == 0) or f32 (numel % 4 == 0)."""
     dev = L.require_device(dy, z)
     assert dy.shape == z.shape and dy.dtype == z.dtype and dy.is_contiguous() and z.is_contiguous()
     dz = torch.empty_like(dy)
@@ -834,7 +834,8 @@ def relu_mask_(dx: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
 
 
 def relu_mask(dy: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
-    """x > 0 ? dy : 0 into a new tensor (contiguous 16-bit, same shape): ReLU backward that leaves the incoming gradient intact."""
+    """x > 0 ? dy : 0 into a new tensor (contiguous f16 / bf16 with numel % 8 == 0 or f32 with numel % 4 == 0, same shape): ReLU backward that
+    leaves the incoming gradient intact."""
     dev = L.require_device(dy, x)
     assert dy.shape == x.shape and dy.dtype == x.dtype and dy.is_contiguous() and x.is_contiguous()
     out = torch.empty_like(dy)
@@ -957,7 +958,7 @@ def conv3x3_backward(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, *, relu
 
 
 def upsample2x_backward_nhwc(dout: torch.Tensor) -> torch.Tensor:
-    """Backward of upsample2x_nhwc (no add): dout [N,2H,2W,C] contiguous 16-bit -> din [N,H,W,C]."""
+    """Backward of upsample2x_nhwc (no add): dout [N,2H,2W,C] contiguous f16 / bf16 (C % 8 == 0) or f32 (C % 4 == 0) -> din [N,H,W,C]."""
     dev = L.require_device(dout)
     assert dout.dim() == 4 and dout.is_contiguous() and dout.dtype in (torch.float16, torch.bfloat16, torch.float32)
     N, Ho, Wo, Cc = dout.shape
