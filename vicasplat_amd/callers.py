@@ -17,7 +17,9 @@ scripts do around the encoder/decoder:
   * `LossLpips` — src/loss/loss_lpips.py:27-54 (published LPIPS-VGG algorithm; the pretrained weights must be supplied, see the class)
   * `LpipsVgg`, `compute_lpips` — lpips.LPIPS(net="vgg") and src/evaluation/metrics.py:37-44 on the HIP kernels (LossLpips(backend="hip"))
   * `Regr3D`, `distillation_loss` — src/loss/loss_conf_point.py:188-252 and the glue of model_wrapper.py:260-299 (training stage 1: the point loss
-    against a DUSt3R / MASt3R teacher's outputs, which enter as tensors) on csrc/distill.hip; `training_step(distill=...)` applies it
+    against a DUSt3R teacher's outputs) on csrc/distill.hip; `training_step(distill=...)` applies it
+  * `sample_anchor_frames`, `distill_targets` — model_wrapper.py:153-182, 248-271: the anchor frames of a step and the teacher's targets for it,
+    from vicasplat_amd.model.distiller (the DUSt3R two-view network on the HIP kernels; its tail is csrc/teacher.hip)
   * `LossDepth`, `depth_smoothness_loss` — src/loss/loss_depth.py:26-60 (edge-aware first / second differences of the rendered depth between
     log(near) and log(far)) on csrc/depth_loss.hip; plugs into `training_step(extra_losses=[...])` and drives the rasterizer's dL_ddepth
   * `configure_optimizer`, `training_step` — ModelWrapper.configure_optimizers / training_step (model_wrapper.py:884-951,
@@ -705,7 +707,8 @@ def compute_lpips(ground_truth: Tensor, predicted: Tensor, net: LpipsVgg) -> Ten
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # distillation point loss -- src/loss/loss_conf_point.py:188-252 (Regr3D) as ModelWrapper.training_step applies it
-# (model_wrapper.py:248-301).  The teacher network is out of scope: its points and confidences enter as tensors.
+# (model_wrapper.py:248-301).  The teacher is vicasplat_amd.model.distiller (get_distiller); `distill_targets` samples the anchor frames, runs
+# it and returns what `training_step(distill=...)` takes.  Points and confidences of any other teacher still enter as tensors.
 # ---------------------------------------------------------------------------------------------------------------------------
 class Regr3D(torch.nn.Module):
     """The reference's Regr3D: pixels whose pseudo-GT distance lies within the [1 %, 99 %] quantiles of their view (per batch element,
@@ -756,20 +759,59 @@ class Regr3D(torch.nn.Module):
         return loss
 
 
+def sample_anchor_frames(video_frames: Tensor, temporal_compression: int = 4, n_frames: int | None = None):
+    """ModelWrapper._sample_anchor_frames (model_wrapper.py:153-182): two anchor frames per scene from adjacent segments of
+    `temporal_compression` frames, with the same np.random draws in the same order (a caller who seeds numpy gets the reference's indices).
+    video_frames [B, V, C, H, W] -> (anchor_frames [B, 2, C, H, W], idx [B, 2], segment_idx [B, 2]), the indices int64 on the frames' device.
+    An odd number of frames treats the first as the reference frame: the segments start after it and the indices shift back, clamped at 0."""
+    B, V, C, H, W = video_frames.shape
+    odd = V % 2 != 0
+    n_segments = (V - 1) // temporal_compression + 1 if odd else V // temporal_compression
+    n_frames = n_frames or n_segments
+    if n_frames != 2:
+        raise ValueError(f"sample_anchor_frames: the teacher takes two frames, got n_frames = {n_frames} ({V} frames in segments of {temporal_compression})")
+    idx = torch.from_numpy(np.random.choice(temporal_compression, (B, n_frames))).long().to(video_frames.device)
+    seg = np.stack([np.random.choice(n_segments - 1, (n_frames - 1,), replace=False) for _ in range(B)], axis=0)
+    segment_idx = torch.from_numpy(seg).long().to(video_frames.device)
+    segment_idx = torch.cat([segment_idx, segment_idx + 1], dim=-1)
+    idx = idx + segment_idx * temporal_compression
+    if odd:
+        idx = (idx + 1 - temporal_compression).clamp_min(0).long()
+    anchor_frames = torch.gather(video_frames, 1, idx[..., None, None, None].expand(-1, -1, C, H, W))
+    return anchor_frames, idx, segment_idx
+
+
+def distill_targets(distiller, context: dict, **extra) -> dict:
+    """The `distill` argument of `training_step` from the images alone (model_wrapper.py:248-271): samples two anchor frames per scene
+    (n_frames=2, temporal_compression=1), runs the frozen teacher on them with the first anchor's extrinsics as the tail kernel's transform
+    -- the teacher's points leave the kernel already in the first video frame's space, so the dict carries pts_in_first_frame=True and
+    `distillation_loss` skips its own einsum -- and returns {pseudo_gt1, pseudo_gt2, frame_idx, segment_idx, pts_in_first_frame}.
+    context: {"image" [B, V, 3, H, W] in [-1, 1], "extrinsics" [B, V, 4, 4]}; `extra` (weight, loss_fn, only) is passed through."""
+    anchors, frame_idx, segment_idx = sample_anchor_frames(context["image"], n_frames=2, temporal_compression=1)
+    E = torch.gather(context["extrinsics"].float(), 1, frame_idx[:, :1, None, None].expand(-1, 1, 4, 4)).squeeze(1)
+    with torch.no_grad():
+        gt1, gt2 = distiller({"image": anchors}, False, transform=E[:, :3])
+    return dict(pseudo_gt1=gt1, pseudo_gt2=gt2, frame_idx=frame_idx, segment_idx=segment_idx, pts_in_first_frame=True, **extra)
+
+
 def distillation_loss(out: dict, pseudo_gt1: dict, pseudo_gt2: dict, frame_idx: Tensor, segment_idx: Tensor, context_extrinsics: Tensor,
-                      weight: float = 1.0, loss_fn: Regr3D | None = None) -> Tensor:
+                      weight: float = 1.0, loss_fn: Regr3D | None = None, pts_in_first_frame: bool = False) -> Tensor:
     """The distillation term of ModelWrapper.training_step (model_wrapper.py:260-299) from the teacher's outputs.
     out: the encoder's outputs (`gaussian_centers` [B,V,H,W,3], `confidence` [B,V,H,W] or None); pseudo_gt1 / pseudo_gt2: the teacher's
     {"pts3d" [B,H,W,3], "conf" [B,H,W]} for the two anchor frames, in the first anchor's camera space; frame_idx [B,2] (int64): the
     anchors' frame numbers; segment_idx [B,2] (int64): the views whose predictions they are compared with; context_extrinsics [B,V,4,4].
     The teacher's points are moved into the first video frame's space by the first anchor's extrinsics; the points are normalised when
     the video has more than two views; the result is multiplied by `weight` (train.distill_weight).  `loss_fn`: a Regr3D (default: the
-    HIP backend)."""
+    HIP backend).  pts_in_first_frame: the teacher's points are in the first video frame's space already (the teacher's tail kernel moved
+    them: `distill_targets`), so they are taken as they are."""
     loss_fn = Regr3D() if loss_fn is None else loss_fn
-    E = torch.gather(context_extrinsics.float(), 1, frame_idx[:, :1, None, None].expand(-1, 1, 4, 4)).squeeze(1)
-    R, t = E[:, :3, :3], E[:, None, None, :3, 3]
-    gt1 = torch.einsum("bij,bhwj->bhwi", R, pseudo_gt1["pts3d"].float()) + t
-    gt2 = torch.einsum("bij,bhwj->bhwi", R, pseudo_gt2["pts3d"].float()) + t
+    if pts_in_first_frame:
+        gt1, gt2 = pseudo_gt1["pts3d"].float(), pseudo_gt2["pts3d"].float()
+    else:
+        E = torch.gather(context_extrinsics.float(), 1, frame_idx[:, :1, None, None].expand(-1, 1, 4, 4)).squeeze(1)
+        R, t = E[:, :3, :3], E[:, None, None, :3, 3]
+        gt1 = torch.einsum("bij,bhwj->bhwi", R, pseudo_gt1["pts3d"].float()) + t
+        gt2 = torch.einsum("bij,bhwj->bhwi", R, pseudo_gt2["pts3d"].float()) + t
     xyz, conf = out["gaussian_centers"], out.get("confidence")
     pr1, pr2 = torch.gather(xyz, 1, segment_idx[..., None, None, None].expand(-1, -1, *xyz.shape[-3:])).unbind(1)
     pc1 = pc2 = None
@@ -878,7 +920,8 @@ def training_step(encoder, decoder, batch: dict, optimizer, *, scheduler=None, c
     `forward_fn(encoder, image, intrinsics, compute_dtype, global_step=) -> dict` replaces the HIP training forward (tests drive the
     step's control flow -- loss scaling, gradient exchange, clipping, skipping -- with a toy encoder / decoder on CPU).
     `distill`: the distillation stage (model_wrapper.py:248-301) -- a dict with the arguments of `distillation_loss` (pseudo_gt1, pseudo_gt2,
-    frame_idx, segment_idx; optional weight, loss_fn; the extrinsics are the context's) and `only`.  The term enters the result as
+    frame_idx, segment_idx; optional weight, loss_fn, pts_in_first_frame; the extrinsics are the context's) and `only`; `distill_targets` makes
+    it from the images alone with the package's teacher.  The term enters the result as
     `loss_distill`.  With `only` (distill_only, stage 1 of the recipe) the forward runs with distill=True, nothing is rendered, only the
     camera and distillation terms are summed and the result has no `psnr` (the reference's distill_only keeps the camera term alone of
     its losses: `extra_losses` have no render to work on there and passing any raises); without it the term is added to the usual
@@ -922,7 +965,8 @@ def training_step(encoder, decoder, batch: dict, optimizer, *, scheduler=None, c
         parts[getattr(fn, "__name__", f"extra{i}")] = fn(render, batch, out)
     if distill is not None:
         parts["distill"] = distillation_loss(out, distill["pseudo_gt1"], distill["pseudo_gt2"], distill["frame_idx"], distill["segment_idx"],
-                                             ctx["extrinsics"], distill.get("weight", 1.0), distill.get("loss_fn"))
+                                             ctx["extrinsics"], distill.get("weight", 1.0), distill.get("loss_fn"),
+                                             pts_in_first_frame=bool(distill.get("pts_in_first_frame", False)))
     loss = sum(parts.values())
     (loss * scale).backward()
     params = [p for p in encoder.parameters() if p.requires_grad]

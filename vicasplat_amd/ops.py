@@ -1536,3 +1536,30 @@ def depth_smooth_backward(d_depth_unit: torch.Tensor, grad_loss: torch.Tensor) -
     out = torch.empty_like(d_depth_unit)
     L.call("vsl_depth_smooth_backward", dev, L.ptr(d_depth_unit), L.ptr(g), N, H, W, L.ptr(out))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the distillation teacher's tail (csrc/teacher.hip, include/vicasplat_teacher.h)
+# ---------------------------------------------------------------------------------------------------------------------------
+def points_conf(raw: torch.Tensor, transform: Optional[torch.Tensor] = None, *, out_pts: Optional[torch.Tensor] = None,
+                out_conf: Optional[torch.Tensor] = None):
+    """(pts [n, H, W, 3] f32, conf [n, H, W] f32) of the raw four-channel pts3d head output raw [n, H, W, 4] (f32 or f16, contiguous: what
+    forward_pts3d_raw returns before its permute): p = xyz / max(|xyz|, 1e-8) * expm1(|xyz|), conf = 1 + exp(c), and with transform
+    [n, 3, 4] (rows of (R | t), f32) pts = R p + t (vst_points_conf).  out_pts / out_conf: contiguous f32 tensors to write into.  No host
+    synchronisation."""
+    dev = L.require_device(raw, transform, out_pts, out_conf)
+    if raw.dim() != 4 or raw.shape[-1] != 4 or raw.numel() == 0 or raw.dtype not in (torch.float32, torch.float16) or not raw.is_contiguous():
+        raise ValueError(f"points_conf takes the contiguous f32 or f16 head output [n, H, W, 4], got {tuple(raw.shape)} {raw.dtype} "
+                         f"(strides {raw.stride()})")
+    n, H, W, _ = raw.shape
+    if transform is not None:
+        if tuple(transform.shape) != (n, 3, 4):
+            raise ValueError(f"points_conf: expected a transform of shape {(n, 3, 4)}, got {tuple(transform.shape)}")
+        transform = transform.detach().float().contiguous()
+    pts = torch.empty(n, H, W, 3, dtype=torch.float32, device=dev) if out_pts is None else out_pts
+    conf = torch.empty(n, H, W, dtype=torch.float32, device=dev) if out_conf is None else out_conf
+    for name, t, shape in (("out_pts", pts, (n, H, W, 3)), ("out_conf", conf, (n, H, W))):
+        if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"points_conf: {name} must be a contiguous f32 tensor of shape {shape}, got {tuple(t.shape)} {t.dtype}")
+    L.call("vst_points_conf", dev, L.ptr(raw), int(raw.dtype == torch.float16), L.ptr(transform), n, H, W, L.ptr(pts), L.ptr(conf))
+    return pts, conf
