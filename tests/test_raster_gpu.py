@@ -569,7 +569,7 @@ def test_camera_twist_gradient_finite_differences_at_full_size():
 
 
 def test_camera_lists_many_cameras_two_scenes():
-    """preprocess / preprocess_backward build each scene's camera list per block in chunks of 2048 cameras: 2200 cameras over two scenes
+    """preprocess builds each scene's camera list per block in chunks of 2048 cameras, preprocess_backward in chunks of 512: 2200 cameras over two scenes
     with an irregular camera -> scene map (every camera rendered against the oracle's per-view result for ITS scene), forward state
     bit-identical, and the Gaussian gradients of the batched backward equal to the sum of the per-camera oracle gradients."""
     from vicasplat_amd.raster import forward_debug, rasterize

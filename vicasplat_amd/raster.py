@@ -142,29 +142,41 @@ def forward_debug(means3D, cov3D, opacities, viewmatrix, projmatrix, campos, tan
                 n_contrib=t[L.VS_BUF_N_CONTRIB].view(torch.int32)[:Cn * H * W].view(Cn, H, W), _state=st)
 
 
-def backward_debug(fwd: dict, dL_dcolor, dL_ddepth=None) -> dict:
+def backward_debug(fwd: dict, dL_dcolor, dL_ddepth=None, *, fill: Optional[float] = None) -> dict:
     """vs_raster_backward on the state of a forward_debug call, with EVERY output of VsRasterGrads requested (dL_dmeans2D per camera,
-    dL_dcolors_precomp / dL_dshs per scene, dL_dtau): the route is the forward's (checkpoints saved or not)."""
+    dL_dcolors_precomp / dL_dshs per scene, dL_dtau): the route is the forward's (checkpoints saved or not).  Also returns `records`:
+    the [C, P, 10] per-(camera, Gaussian) gradient records the render backward leaves for preprocess_backward_kernel (the entry's
+    VS_BUF_MISC scratch, kept alive past the call; slots: mean2D xy in NDC units, conic A B C, opacity, colour rgb, depth).
+    fill: every gradient output is pre-filled with this value instead of left uninitialised, so that a test can tell the elements
+    the kernel stored from the ones it skipped."""
     st = fwd["_state"]
     S, P, Cn, M, H, W, cov33 = st["dims"]
     inp, out = st["inp"], st["out"]
     dev = fwd["color"].device
     g_color = _f32c(dL_dcolor)
     g_depth = _f32c(dL_ddepth)
-    r = dict(means3D=torch.empty((S, P, 3), dtype=torch.float32, device=dev),
-             cov3D=torch.empty((S, P, 3, 3) if cov33 else (S, P, 6), dtype=torch.float32, device=dev),
-             shs=torch.empty((S, P, M, 3), dtype=torch.float32, device=dev) if inp.shs else None,
-             colors_precomp=torch.empty((S, P, 3), dtype=torch.float32, device=dev) if inp.colors_precomp else None,
-             opacities=torch.empty((S, P), dtype=torch.float32, device=dev),
-             means2D=torch.empty((Cn, P, 2), dtype=torch.float32, device=dev),
-             tau=torch.empty((Cn, 6), dtype=torch.float32, device=dev))
+
+    def new(*shape):
+        if fill is None:
+            return torch.empty(shape, dtype=torch.float32, device=dev)
+        return torch.full(shape, float(fill), dtype=torch.float32, device=dev)
+
+    r = dict(means3D=new(S, P, 3), cov3D=new(S, P, 3, 3) if cov33 else new(S, P, 6),
+             shs=new(S, P, M, 3) if inp.shs else None, colors_precomp=new(S, P, 3) if inp.colors_precomp else None,
+             opacities=new(S, P), means2D=new(Cn, P, 2), tau=new(Cn, 6))
     g = L.VsRasterGrads()
     g.dL_dcolor, g.dL_ddepth = L.ptr(g_color), L.ptr(g_depth)
     g.dL_dmeans3D, g.dL_dcov3D, g.dL_dshs = L.ptr(r["means3D"]), L.ptr(r["cov3D"]), L.ptr(r["shs"])
     g.dL_dcolors_precomp, g.dL_dopacities = L.ptr(r["colors_precomp"]), L.ptr(r["opacities"])
     g.dL_dmeans2D, g.dL_dtau = L.ptr(r["means2D"]), L.ptr(r["tau"])
-    _backward_impl(inp, out, g, dev)
+    alloc = L.TorchAllocator(dev)      # (as _backward_impl, but the scratch outlives the call)
+    try:
+        L.call("vs_raster_backward", dev, C.byref(inp), C.byref(out), C.byref(g), alloc.fn, None)
+    finally:
+        alloc.fn = None
     torch.cuda.synchronize(dev)
+    rec = alloc.tensors.get(L.VS_BUF_MISC)
+    r["records"] = None if rec is None else rec.view(torch.float32)[:Cn * P * 10].view(Cn, P, 10)
     return r
 
 
