@@ -22,6 +22,10 @@ scripts do around the encoder/decoder:
     from vicasplat_amd.model.distiller (the DUSt3R two-view network on the HIP kernels; its tail is csrc/teacher.hip)
   * `LossDepth`, `depth_smoothness_loss` — src/loss/loss_depth.py:26-60 (edge-aware first / second differences of the rendered depth between
     log(near) and log(far)) on csrc/depth_loss.hip; plugs into `training_step(extra_losses=[...])` and drives the rasterizer's dL_ddepth
+  * `camera_eval_metrics` — src/evaluation/metrics.py:148-265 (ATE, RPE-trans, RPE-rot: evo's ape / rpe restated, UNVERIFIED against evo) on
+    csrc/trajectory.hip, batched over scenes, device tensors out
+  * `test_step` — ModelWrapper.test_step, src/model/model_wrapper.py:323-381: the six numbers it logs, per scene, batched
+  * `pose_eval_step` — PoseEvaluator.test_step, src/evaluation/pose_evaluator.py:77-174: the pose metrics before and after refinement
   * `configure_optimizer`, `training_step` — ModelWrapper.configure_optimizers / training_step (model_wrapper.py:884-951,
     184-321): AdamW(lr, wd 0.05, betas 0.9/0.95) with the backbone-lr multiplier, encoder -> rasterizer -> MSE ->
     backward on the HIP kernels (vicasplat_amd.autograd) -> optional gradient all-reduce -> clip 0.5 -> step.
@@ -996,3 +1000,148 @@ def training_step(encoder, decoder, batch: dict, optimizer, *, scheduler=None, c
     res.update(grad_norm=gnorm, skipped=not finite, pred_extrins=out["pred_extrins"].detach(), loss_scale=scale,
                **{"loss_" + k: v.detach() for k, v in parts.items()})
     return res
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# trajectory metrics and the test step -- src/evaluation/metrics.py:148-265, src/model/model_wrapper.py:323-381,
+# src/evaluation/pose_evaluator.py:77-174.  The reference hands every scene to evo on the host (a device -> host copy, a scipy rotation per
+# pose, three evo calls); evo is not available offline, so its ape / rpe (align=True, correct_scale=True, delta in frames, all_pairs=True) are
+# restated from the published algorithm -- Umeyama's alignment, then the residuals -- as include/vicasplat_metrics.h writes it out.
+# ---------------------------------------------------------------------------------------------------------------------------
+# STATUS: UNVERIFIED against evo -- no package, no fixture of its numbers exists offline; the kernel, the torch backend and the float64
+# restatement of tests/trajectory_f64.py agree with one another and with closed forms, which pins the algorithm as stated, not evo's code.
+def _det3(M: Tensor) -> Tensor:
+    return (M[..., 0, 0] * (M[..., 1, 1] * M[..., 2, 2] - M[..., 1, 2] * M[..., 2, 1])
+            - M[..., 0, 1] * (M[..., 1, 0] * M[..., 2, 2] - M[..., 1, 2] * M[..., 2, 0])
+            + M[..., 0, 2] * (M[..., 1, 0] * M[..., 2, 1] - M[..., 1, 1] * M[..., 2, 0]))
+
+
+def _trajectory_metrics_torch(P: Tensor, Q: Tensor, delta: int):
+    """The algorithm of include/vicasplat_metrics.h in plain float64 torch, batched: (metrics [B, 3], valid [B] bool)."""
+    P, Q = P.double(), Q.double()
+    B, V = P.shape[:2]
+    finite = torch.isfinite(P).flatten(1).all(1) & torch.isfinite(Q).flatten(1).all(1)
+    if V < 3 or delta >= V:
+        return torch.zeros(B, 3, dtype=torch.float64, device=P.device), torch.zeros_like(finite)
+    eye = torch.eye(4, dtype=torch.float64, device=P.device)
+    P = torch.where(finite[:, None, None, None], P, eye)       # a non-finite scene must not reach the SVD; it is masked below
+    Q = torch.where(finite[:, None, None, None], Q, eye)
+    x, y, Rp, Rq = P[..., :3, 3], Q[..., :3, 3], P[..., :3, :3], Q[..., :3, :3]
+    mux, muy = x.mean(1), y.mean(1)
+    dx, dy = x - mux[:, None], y - muy[:, None]
+    sig2 = (dx * dx).sum((1, 2)) / V
+    C = torch.einsum("bvi,bvj->bij", dy, dx) / V
+    U, d, Vh = torch.linalg.svd(C)
+    valid = finite & ((d > 2.0 ** -52).sum(1) >= 2)
+    S = torch.ones_like(d)
+    S[:, 2] = torch.where(_det3(U) * _det3(Vh) < 0, -1.0, 1.0)
+    R = (U * S[:, None, :]) @ Vh
+    c = (d * S).sum(1) / sig2
+    t = muy - c[:, None] * (R @ mux[..., None])[..., 0]
+    res = c[:, None, None] * (x @ R.transpose(1, 2)) + t[:, None] - y
+    ate = (res * res).sum(-1).mean(1).sqrt()
+    i, j = slice(0, V - delta), slice(delta, V)
+    A, a = Rq[:, i].transpose(-1, -2) @ Rq[:, j], (Rq[:, i].transpose(-1, -2) @ (y[:, j] - y[:, i])[..., None])[..., 0]
+    Bm, b = Rp[:, i].transpose(-1, -2) @ Rp[:, j], c[:, None, None] * (Rp[:, i].transpose(-1, -2) @ (x[:, j] - x[:, i])[..., None])[..., 0]
+    E, Et = A.transpose(-1, -2) @ Bm, (A.transpose(-1, -2) @ (b - a)[..., None])[..., 0]
+    w = torch.stack([E[..., 2, 1] - E[..., 1, 2], E[..., 0, 2] - E[..., 2, 0], E[..., 1, 0] - E[..., 0, 1]], -1)
+    theta = torch.atan2(0.5 * w.norm(dim=-1), 0.5 * (E.diagonal(dim1=-2, dim2=-1).sum(-1) - 1.0)) * (180.0 / math.pi)
+    out = torch.stack([ate, (Et * Et).sum(-1).mean(1).sqrt(), (theta * theta).mean(1).sqrt()], -1)
+    return torch.where(valid[:, None], out, torch.zeros_like(out)), valid
+
+
+@torch.no_grad()
+def camera_eval_metrics(pred_c2ws: Tensor, gt_c2ws: Tensor, sample_stride: int = 1, *, backend: str | None = None, return_valid: bool = False):
+    """(ate, rpe_trans, rpe_rot) of estimated against true camera-to-world poses, [V, 4, 4] (0-d results) or [B, V, 4, 4] ([B] results), as
+    metrics.py:185-265 asks evo for them: Umeyama alignment with scale, the RMSE of the aligned positions, and the RMSE of the relative pose
+    errors between consecutive frames (translation norm; rotation angle in degrees).  Float64 tensors on the inputs' device, never Python
+    floats; no host synchronisation.  sample_stride > 1 keeps every sample_stride-th pose (:189-196).  A scene evo would refuse (the
+    reference's bare `except` logs 0.0 for it, model_wrapper.py:374-377: collinear or coincident positions, fewer than 3 poses) or one with a
+    non-finite pose gives three zeros; return_valid adds the flag ([B] or 0-d bool) that tells such a scene from a perfect one.
+    backend="hip" (the default for HIP tensors): csrc/trajectory.hip, one launch for the batch; backend="torch" (the default for CPU
+    tensors): the same algorithm in plain float64 torch (CPU tests, the bench tool's comparison).  Half-precision poses are promoted to f32.
+    UNVERIFIED against evo (see above); rotations are used as given, not passed through a quaternion."""
+    if backend is None:
+        backend = "hip" if pred_c2ws.is_cuda else "torch"
+    if backend not in ("torch", "hip"):
+        raise ValueError(f'camera_eval_metrics: backend must be "torch" or "hip", got {backend!r}')
+    single = pred_c2ws.dim() == 3
+    P, Q = (pred_c2ws[None], gt_c2ws[None]) if single else (pred_c2ws, gt_c2ws)
+    if P.dim() != 4 or tuple(P.shape[-2:]) != (4, 4) or P.shape != Q.shape:
+        raise ValueError(f"camera_eval_metrics takes poses [V, 4, 4] or [B, V, 4, 4] of one shape, got {tuple(pred_c2ws.shape)} and "
+                         f"{tuple(gt_c2ws.shape)}")
+    if int(sample_stride) != sample_stride or sample_stride < 1:
+        raise ValueError(f"camera_eval_metrics: sample_stride must be a positive integer, got {sample_stride!r}")
+    if sample_stride > 1:
+        P, Q = P[:, ::sample_stride], Q[:, ::sample_stride]
+    if backend == "hip":
+        from . import ops
+        dt = torch.float64 if torch.float64 in (P.dtype, Q.dtype) else torch.float32
+        m, valid = ops.trajectory_metrics(P.detach().to(dt).contiguous(), Q.detach().to(dt).contiguous(), 1)
+        valid = valid != 0
+    else:
+        m, valid = _trajectory_metrics_torch(P.detach(), Q.detach(), 1)
+    if single:
+        m, valid = m[0], valid[0]
+    out = (m[..., 0], m[..., 1], m[..., 2])
+    return out + (valid,) if return_valid else out
+
+
+def _per_scene(per_image: Tensor, b: int, v: int) -> Tensor:
+    return per_image.unflatten(0, (b, v)).mean(1)
+
+
+def test_step(encoder, decoder, batch: dict, *, lpips_net: LpipsVgg | None = None, align_pose: bool = False, align_kwargs: dict | None = None) -> dict:
+    """ModelWrapper.test_step's scores (model_wrapper.py:323-381), batched over scenes (the reference asserts b == 1): the encoder under
+    no_grad on batch["context"]; the target views rendered from its Gaussians -- with align_pose (test_cfg.align_pose, :339-340) from the
+    target extrinsics `align_poses` refines first (`align_kwargs`: its keyword arguments); then per scene, as device tensors [B]:
+      psnr_ours, ssim_ours, lpips_ours   the means over the scene's target views of compute_psnr / compute_ssim / compute_lpips (:357-364);
+                                         lpips_ours only when `lpips_net` (an LpipsVgg) is given -- its weights are not available offline
+      ate_ours, rpe-trans_ours, rpe-rot_ours   camera_eval_metrics of model_outs["gaussian_camera_extrins"] against
+                                         batch["context"]["extrinsics"] (:367-381), float64
+      pose_valid                         False where the reference's bare `except` would have logged zeros
+    No .item(), no host copy: a caller logs or reduces the tensors when it chooses to.
+    batch: {"context": {"image" [B,V,3,H,W] in [-1,1], "intrinsics", "extrinsics" [B,V,4,4], ...},
+            "target":  {"image" [B,Vt,3,H,W] in [0,1], "extrinsics", "intrinsics", "near", "far"}}"""
+    ctx, tgt = batch["context"], batch["target"]
+    b, v, _, h, w = tgt["image"].shape
+    with torch.no_grad():
+        model_outs = encoder(ctx)
+    gaussians = model_outs["gaussians"]
+    extrinsics = tgt["extrinsics"]
+    if align_pose:
+        extrinsics = align_poses(decoder, gaussians, tgt["image"], extrinsics, tgt["intrinsics"], tgt["near"], tgt["far"], **(align_kwargs or {}))
+    with torch.no_grad():
+        output = decoder.forward(gaussians, extrinsics, tgt["intrinsics"], tgt["near"], tgt["far"], (h, w))
+        rgb_pred, rgb_gt = output.color.flatten(0, 1), tgt["image"].flatten(0, 1)
+        scores = {"psnr_ours": _per_scene(compute_psnr(rgb_gt, rgb_pred), b, v), "ssim_ours": _per_scene(compute_ssim(rgb_gt, rgb_pred), b, v)}
+        if lpips_net is not None:
+            scores["lpips_ours"] = _per_scene(compute_lpips(rgb_gt, rgb_pred, lpips_net), b, v)
+        ate, rpe_trans, rpe_rot, valid = camera_eval_metrics(model_outs["gaussian_camera_extrins"], ctx["extrinsics"], return_valid=True)
+        scores.update({"ate_ours": ate, "rpe-trans_ours": rpe_trans, "rpe-rot_ours": rpe_rot, "pose_valid": valid})
+    return scores
+
+
+def pose_eval_step(encoder, decoder, batch: dict, *, steps: int = 0, rot_lr: float = 0.005, trans_lr: float = 0.005, mse_weight: float = 1.0,
+                   ssim_structure_weight: float = 1.0, sample_stride: int = 1) -> dict:
+    """PoseEvaluator.test_step (pose_evaluator.py:77-174), batched over scenes: the encoder under no_grad; the predicted poses of the context
+    views other than the first refined by `steps` of `align_poses` against those views' own images (image * 0.5 + 0.5) with the SSIM
+    structure term on (:136-141) -- steps = 0, as the reference ships it (number_steps = 0, :112), refines nothing --; then
+    camera_eval_metrics of [true first pose | refined poses] (:159) and of the unrefined prediction against batch["context"]["extrinsics"].
+    Returns per-scene float64 device tensors [B]: ate / rpe_trans / rpe_rot _after_opt and _before_opt, and pose_valid_after_opt /
+    pose_valid_before_opt.  No host copy."""
+    ctx = batch["context"]
+    with torch.no_grad():
+        model_outs = encoder(ctx)
+    pred = model_outs["gaussian_camera_extrins"]
+    extrinsics = pred[:, 1:].clone()
+    if steps > 0:
+        extrinsics = align_poses(decoder, model_outs["gaussians"], ctx["image"][:, 1:] * 0.5 + 0.5, extrinsics, ctx["intrinsics"][:, 1:],
+                                 ctx["near"][:, 1:], ctx["far"][:, 1:], steps=steps, rot_lr=rot_lr, trans_lr=trans_lr, mse_weight=mse_weight,
+                                 ssim_structure_weight=ssim_structure_weight)
+    gt = ctx["extrinsics"]
+    eval_pose = torch.cat([gt[:, :1].to(extrinsics.dtype), extrinsics.detach()], dim=1)
+    after = camera_eval_metrics(eval_pose, gt, sample_stride, return_valid=True)
+    before = camera_eval_metrics(pred, gt, sample_stride, return_valid=True)
+    names = ("ate", "rpe_trans", "rpe_rot", "pose_valid")
+    return {**{f"{n}_after_opt": t for n, t in zip(names, after)}, **{f"{n}_before_opt": t for n, t in zip(names, before)}}

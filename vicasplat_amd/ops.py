@@ -1563,3 +1563,36 @@ def points_conf(raw: torch.Tensor, transform: Optional[torch.Tensor] = None, *, 
             raise ValueError(f"points_conf: {name} must be a contiguous f32 tensor of shape {shape}, got {tuple(t.shape)} {t.dtype}")
     L.call("vst_points_conf", dev, L.ptr(raw), int(raw.dtype == torch.float16), L.ptr(transform), n, H, W, L.ptr(pts), L.ptr(conf))
     return pts, conf
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# trajectory metrics (csrc/trajectory.hip, include/vicasplat_metrics.h)
+# ---------------------------------------------------------------------------------------------------------------------------
+_TRAJ_DTYPES = {torch.float32: 0, torch.float64: 5}      # the dtype codes of vsm_trajectory_metrics
+
+
+def trajectory_metrics(pred: torch.Tensor, gt: torch.Tensor, delta: int = 1, return_alignment: bool = False):
+    """(metrics [B, 3] f64 = ate, rpe_trans, rpe_rot (degrees); valid [B] int32) of estimated against true camera-to-world poses, both
+    [B, V, 4, 4], contiguous, f32 or f64 (one dtype for both), on a HIP device: Umeyama alignment with scale, then ATE and the relative pose
+    errors over the pairs (i, i + delta) (vsm_trajectory_metrics; the algorithm is written out in include/vicasplat_metrics.h).  A degenerate
+    scene -- fewer than two singular values above 2^-52, V < 3, delta >= V, a non-finite element -- has valid 0, metrics 0 and the identity as
+    its alignment.  return_alignment: also align [B, 13] f64 = R row-major, t, c.  One launch on the current stream, no host synchronisation."""
+    dev = L.require_device(pred, gt)
+    if pred.dim() != 4 or tuple(pred.shape[-2:]) != (4, 4) or pred.shape[1] < 1:
+        raise ValueError(f"trajectory_metrics takes poses [B, V, 4, 4] with V >= 1, got {tuple(pred.shape)}")
+    if gt.shape != pred.shape:
+        raise ValueError(f"trajectory_metrics: expected ground truth of shape {tuple(pred.shape)}, got {tuple(gt.shape)}")
+    if pred.dtype not in _TRAJ_DTYPES or gt.dtype != pred.dtype:
+        raise ValueError(f"trajectory_metrics takes f32 or f64 poses of one dtype, got {pred.dtype} and {gt.dtype}")
+    if not (pred.is_contiguous() and gt.is_contiguous()):
+        raise ValueError(f"trajectory_metrics takes contiguous poses, got strides {pred.stride()} and {gt.stride()}")
+    if int(delta) != delta or delta < 1:
+        raise ValueError(f"trajectory_metrics: delta must be a positive number of frames, got {delta!r}")
+    B, V = pred.shape[:2]
+    metrics = torch.empty(B, 3, dtype=torch.float64, device=dev)
+    valid = torch.empty(B, dtype=torch.int32, device=dev)
+    align = torch.empty(B, 13, dtype=torch.float64, device=dev) if return_alignment else None
+    if B > 0:       # (an empty tensor has no address to hand over)
+        L.call("vsm_trajectory_metrics", dev, L.ptr(pred.detach()), L.ptr(gt.detach()), _TRAJ_DTYPES[pred.dtype], B, V,
+               min(int(delta), 2 ** 31 - 1), L.ptr(metrics), L.ptr(valid), L.ptr(align))
+    return (metrics, valid, align) if return_alignment else (metrics, valid)
