@@ -179,7 +179,8 @@ int vs_conv3x3_split_res2_nhwc(const float *in, const void *wp, float acc_scale,
                                float *out, int32_t Nimg, int32_t Hin, int32_t Win, int32_t Cin, int32_t Cout, int32_t stride, int32_t relu_in,
                                int32_t relu_out, vs_stream_t stream);
 /* vs_gemm_split with the A operand ALREADY in the packed (hi, lo) form (Ap = vs_split_pack_weight(A, scale_exp 0) or a producer that
- * writes that form; lda in 4-byte units): the main loops skip the in-kernel conversion.  M > 64 routes only (tile kernels). */
+ * writes that form; lda in 4-byte units): the main loops skip the in-kernel conversion.  Every route takes it: M <= 64 goes to the
+ * weight-streaming kernel, which reads packed rows as well (the RoPE epilogue and packed outputs of such an M: the skinny kernel). */
 int vs_gemm_split_packed(const void *Ap, const void *Wp, float acc_scale, const float *bias, float *out, const float *gate, const float *resid,
                          int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldw, int32_t ldo, int32_t epilogue, int32_t grp_in, int32_t grp_out,
                          int32_t grp_off, int32_t gate_rows, int32_t gate_ld, int32_t a_grp_in, int32_t a_grp_out, int32_t a_grp_off,

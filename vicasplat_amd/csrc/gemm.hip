@@ -699,6 +699,7 @@ int launch_f32(const GemmArgs &g, int epi, hipStream_t stream) {
     return launch_mi<kDtF32, 4>(g, epi, stream);
 }
 
+// (tests/gemm_f64.py, plan(), transcribes this dispatcher -- launch, launch_tail, launch_f32, launch_skinny, launch_smallm -- line by line: change them together)
 template <int BF16>
 int launch(const GemmArgs &g, int epi, hipStream_t stream) {
     if (g.M <= 64 && epi != 4 && epi != 5 && !g.out_packed && (BF16 == kDtSplit || !g.a_packed)) return launch_smallm<BF16>(g, epi, stream);
@@ -911,6 +912,17 @@ int gemm_entry(const char *fn, const void *A, const void *W, const float *bias, 
     g.rope_pos = rope_pos; g.rope_kind = rope_kind; g.rope_C = rope_C;
     g.rope_l2base = base2d > 0.f ? log2f(base2d) : 0.f;
     g.rope_l2theta = theta1d > 0.f ? log2f(theta1d) : 0.f;
+    if (rope_pos) {   // frequencies of the positions behind the epilogue's table, in revolutions, as (hi, lo) pairs (GemmArgs::rope2_u ...)
+        const double inv2pi = 0.15915494309189533577;
+        auto pair = [](double v, float (&o)[2]) { o[0] = (float)v; o[1] = (float)(v - (double)o[0]); };
+        for (int r = 0; r < 4; ++r) {
+            pair(pow((double)base2d, -r / 16.0) * inv2pi, g.rope2_u[r]);
+            pair(pow((double)base2d, -4.0 * r / 16.0), g.rope2_l[r]);
+            pair(pow((double)theta1d, -2.0 * r / 32.0), g.rope1_l[r]);
+        }
+        for (int j = 0; j < 4; ++j)
+            for (int t = 0; t < 2; ++t) pair(pow((double)theta1d, -(8.0 * j + t) / 32.0) * inv2pi, g.rope1_u[2 * j + t]);
+    }
     g.acc_scale = acc_scale;
     g.a_packed = a_packed;
     g.out_packed = out_packed;

@@ -56,6 +56,11 @@ struct GemmArgs {
     const uint8_t *rope_kind = nullptr;
     int rope_C = 0;  // columns [0, C) = q, [C, 2C) = k, rest untouched
     float rope_l2base = 0.f, rope_l2theta = 0.f;  // log2 of the 2-D base / 1-D theta
+    // positions behind the (sin, cos) table (pos >= 64): the f32 angle p * base^(-i / 16) carries about p * 2e-7 rad (1e-4 rad at p = 1000), so
+    // those take their frequency, in revolutions, as the product of two (hi, lo) float pairs that the entry point computes in double --
+    // an unrolled part u and a lane part l: 2-D i = 4 g + r: u[r] = base^(-r / 16) / 2 pi, l[g] = base^(-4 g / 16); 1-D pair index
+    // q = 8 j + 2 g + s: u[2 j + s] = theta^(-(8 j + s) / 32) / 2 pi, l[g] = theta^(-2 g / 32)
+    float rope2_u[4][2] = {}, rope2_l[4][2] = {}, rope1_u[8][2] = {}, rope1_l[4][2] = {};
     int tap_on_a = 0;     // tap-fused weight gradient: the tap shift moves the A operand instead of W (split class: a packed W cannot be shifted)
     int out_packed = 0;   // split operands, epilogues 0 / 1 / 3: the output is written in the packed (hi, lo) form (the A operand of the next GEMM)
     int a_packed = 0;     // split operands: A is ALREADY in the packed (hi, lo) form of vs_split_pack_weight (scale 2^0): the kernels skip the conversion
@@ -341,6 +346,19 @@ __device__ __forceinline__ void sincos_hw(float ang, float &sn, float &cs) {
     cs = __builtin_amdgcn_cosf(rev);
 }
 
+// sin / cos of p * (u * l) revolutions, u and l (hi, lo) float pairs: product and angle carried in two floats, the whole revolutions taken off
+// exactly (RoPE positions behind the table; p an integer below 2^24)
+__device__ __forceinline__ void sincos_far(float p, const float (&u)[2], float lh, float ll, float &sn, float &cs) {
+#pragma clang fp contract(off)   // (kh and ph must be the ROUNDED products: fused into the fma below, their residuals would come out as zero)
+    const float kh = u[0] * lh;
+    const float kl = __builtin_fmaf(u[0], lh, -kh) + (u[0] * ll + u[1] * lh);
+    const float ph = p * kh;
+    const float pe = __builtin_fmaf(p, kh, -ph) + p * kl;
+    const float rev = (ph - __builtin_rintf(ph)) + pe;
+    sn = __builtin_amdgcn_sinf(rev);
+    cs = __builtin_amdgcn_cosf(rev);
+}
+
 // XOR swizzle of the 16-byte chunk index (0..3) inside a 64-byte LDS row, keyed on (row >> 2) & 3, chosen so that the
 // four 16-lane service groups of ds_read_b128 each touch 16 distinct 16-byte slots of a 256-byte bank row.
 __device__ __forceinline__ int swz4(int row) { return (0x1320 >> (((row >> 2) & 3) * 4)) & 3; }  // f = {0,2,3,1}
@@ -393,7 +411,13 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &g, f4 (&acc)[MI][4
     // path -- with the SAME expression the direct evaluation uses, so the results are bit-identical; larger positions fall back to it.
     constexpr int kRopeTabPos = 64;
     [[maybe_unused]] float2 *const rtab = reinterpret_cast<float2 *>(lds_scratch);
+    [[maybe_unused]] float far2h = 0.f, far2l = 0.f, far1h = 0.f, far1l = 0.f;   // lane parts of the far positions' frequencies (sincos_far)
     if constexpr (EPI == 4) {
+        const int lg = lane >> 4;
+        far2h = lg == 0 ? g.rope2_l[0][0] : lg == 1 ? g.rope2_l[1][0] : lg == 2 ? g.rope2_l[2][0] : g.rope2_l[3][0];
+        far2l = lg == 0 ? g.rope2_l[0][1] : lg == 1 ? g.rope2_l[1][1] : lg == 2 ? g.rope2_l[2][1] : g.rope2_l[3][1];
+        far1h = lg == 0 ? g.rope1_l[0][0] : lg == 1 ? g.rope1_l[1][0] : lg == 2 ? g.rope1_l[2][0] : g.rope1_l[3][0];
+        far1l = lg == 0 ? g.rope1_l[0][1] : lg == 1 ? g.rope1_l[1][1] : lg == 2 ? g.rope1_l[2][1] : g.rope1_l[3][1];
         rope_on = nbase < 2 * g.rope_C && full_n;
 #pragma unroll
         for (int r = 0; r < 4; ++r) inv2d[r] = __builtin_amdgcn_exp2f(-(float)(c4 + r) * (1.0f / 16.0f) * g.rope_l2base);
@@ -534,7 +558,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &g, f4 (&acc)[MI][4
                                             sn = r == 0 ? sc01.x : r == 1 ? sc01.z : r == 2 ? sc23.x : sc23.z;
                                             cs = r == 0 ? sc01.y : r == 1 ? sc01.w : r == 2 ? sc23.y : sc23.w;
                                         } else {
-                                            sincos_hw(p * inv2d[r], sn, cs);
+                                            sincos_far(p, g.rope2_u[r], far2h, far2l, sn, cs);
                                         }
                                         const float u = v[2 * h][r], w = v[2 * h + 1][r];
                                         v[2 * h][r] = u * cs - w * sn;
@@ -543,12 +567,14 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &g, f4 (&acc)[MI][4
                                 }
                             } else if (rk[i] == 1) {
                                 const float p = (float)rp[i].x;
+                                const bool far = (unsigned)rp[i].x >= (unsigned)kRopeTabPos;
 #pragma unroll
                                 for (int j = 0; j < 4; ++j)
 #pragma unroll
                                     for (int r = 0; r < 4; r += 2) {
                                         float sn, cs;
-                                        sincos_hw(p * __builtin_amdgcn_exp2f(-(float)((j * 16 + c4 + r) >> 1) * (1.0f / 32.0f) * g.rope_l2theta), sn, cs);
+                                        if (far) sincos_far(p, g.rope1_u[2 * j + (r >> 1)], far1h, far1l, sn, cs);
+                                        else sincos_hw(p * __builtin_amdgcn_exp2f(-(float)((j * 16 + c4 + r) >> 1) * (1.0f / 32.0f) * g.rope_l2theta), sn, cs);
                                         const float u = v[j][r], w = v[j][r + 1];
                                         v[j][r] = u * cs - w * sn;
                                         v[j][r + 1] = w * cs + u * sn;
@@ -637,11 +663,14 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &g, f4 (&acc)[MI][4
                 if (kd == 0) {
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
-                        const float p = (float)(h == 0 ? pp.x : pp.y);
+                        const int pi = h == 0 ? pp.x : pp.y;
+                        const float p = (float)pi;
+                        const bool far = (unsigned)pi >= (unsigned)kRopeTabPos;    // (the same split as the wide path: results do not depend on the tile path)
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             float sn, cs;
-                            sincos_hw(p * inv2d[r], sn, cs);
+                            if (far) sincos_far(p, g.rope2_u[r], far2h, far2l, sn, cs);
+                            else sincos_hw(p * inv2d[r], sn, cs);
                             const float u = v[2 * h][r], w = v[2 * h + 1][r];
                             v[2 * h][r] = u * cs - w * sn;
                             v[2 * h + 1][r] = w * cs + u * sn;
@@ -649,12 +678,14 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &g, f4 (&acc)[MI][4
                     }
                 } else if (kd == 1) {  // temporal rope of a camera-token row: interleaved pairs (2p, 2p+1) = registers (r, r+1)
                     const float p = (float)pp.x;
+                    const bool far = (unsigned)pp.x >= (unsigned)kRopeTabPos;
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
 #pragma unroll
                         for (int r = 0; r < 4; r += 2) {
                             float sn, cs;
-                            sincos_hw(p * __builtin_amdgcn_exp2f(-(float)((j * 16 + c4 + r) >> 1) * (1.0f / 32.0f) * g.rope_l2theta), sn, cs);
+                            if (far) sincos_far(p, g.rope1_u[2 * j + (r >> 1)], far1h, far1l, sn, cs);
+                            else sincos_hw(p * __builtin_amdgcn_exp2f(-(float)((j * 16 + c4 + r) >> 1) * (1.0f / 32.0f) * g.rope_l2theta), sn, cs);
                             const float u = v[j][r], w = v[j][r + 1];
                             v[j][r] = u * cs - w * sn;
                             v[j][r + 1] = w * cs + u * sn;
