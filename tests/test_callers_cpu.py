@@ -330,10 +330,12 @@ def test_split_class_training_step_defaults_and_operand_geometry():
     # zero-bordered pixel grid of the tap-fused weight gradient: N images of (H + 2) x (W + 2) pixels; halo >= largest |tap shift| + 1, 16-byte rows
     assert ops._border_rows(2 * 5 * 7, (5, 7), True) == 2 * 7 * 9 and ops._border_rows(70, (5, 7), False) == 70
     for W in (4, 16, 37, 256):
-        Wp = W + 2
-        halo = (Wp + 2 + 3) // 4 * 4
-        shifts = [(ty - 1) * Wp + (tx - 1) for ty in range(3) for tx in range(3)]
-        assert halo % 4 == 0 and halo > max(abs(s) for s in shifts)
+        for align in (4, 8):            # elements per 16 bytes: f32 (conv3x3_backward_split) / 16-bit (conv3x3_backward)
+            shifts, halo = ops.bordered_taps(W, align)
+            assert halo % align == 0 and halo > max(abs(s) for s in shifts)
+            # nine taps in (ty, tx) order over (W + 2)-wide rows: up-left ... centre ... down-right
+            assert len(shifts) == 9 and shifts == sorted(shifts) and shifts[4] == 0 and shifts[0] == -(W + 3) and shifts[3] == -1
+            assert all(shifts[i] == -shifts[8 - i] for i in range(9)) and shifts[1] - shifts[0] == 1 and shifts[3] - shifts[0] == W + 2
 
 
 def test_boundary_grad_scale_leaves_plain_gradients_and_handles_accumulation():

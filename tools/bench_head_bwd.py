@@ -19,7 +19,7 @@ for Cin, Cout in ((256, 83), (128, 3)):
     dy = torch.randn(P, Cout, device=d)
     w = torch.randn(Cout, Cin, device=d) * 0.05
     e = ops.split_scale_exp(w)
-    ms = timeit(lambda: ops.head1x1_backward_split(dy, t, w, relu=True, scale_exp=e))
+    ms = timeit(lambda: ops.head1x1_backward(dy, t, w, relu=True, scale_exp=e))
     gb = P * (Cout + 2 * Cin) * 4 / 1e9
     def old():
         dx, dw, db = ops.linear_backward_split(dy, t, w, scale_exp=e)

@@ -12,6 +12,8 @@ from typing import Optional
 import torch
 
 from . import _lib as L
+from .backward_routes import bordered_taps, conv3x3_backward_route, linear_backward_route, round_up
+from .backward_routes import wgrad_ksplit  # noqa: F401  (ops.wgrad_ksplit: tools/bench_wgrad.py, tests)
 
 _DT = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 # operand dtype codes of the MFMA kernels (GEMM / convolution / attention / upsample): 3 = f32, the reference-precision path --
@@ -669,19 +671,6 @@ def transpose16(x: torch.Tensor, pad_to: int = 1, *, colsum_out: Optional[torch.
     return out
 
 
-def wgrad_ksplit(out_rows: int, out_cols: int, red: int, ntaps: int = 1) -> tuple[int, int]:
-    """(ksplit, reduction padding unit) of a weight-gradient GEMM out[out_rows, out_cols] = sum over `red` rows.  Mirrors the
-    dispatch of vs_gemm_splitk_accumulate: whole 256x256 output tiles run on the 8-wave kernel, one workgroup per CU (aim at
-    ~256 workgroups, K slices of an even number of 64-wide tiles); anything else on 128x128 tiles, 3 per CU (~768)."""
-    if out_rows % 256 == 0 and out_cols % 256 == 0:
-        tiles = (out_rows // 256) * (out_cols // 256) * ntaps
-        ks = max(1, min((256 + tiles // 2) // tiles, red // 512))
-        return ks, 128 * ks
-    tiles = ((out_rows + 127) // 128) * ((out_cols + 127) // 128) * ntaps
-    ks = max(2, min(768 // tiles, red // 512, 1024))
-    return ks, 64 * ks
-
-
 def colsum(x: torch.Tensor) -> torch.Tensor:
     """f32 column sums of x [M,N] (f32 / f16 / bf16)."""
     dev = L.require_device(x)
@@ -792,36 +781,29 @@ def linear_backward(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, *, need_
     M, N = dy.shape
     K = x.shape[1]
     dev = dy.device
+    r = linear_backward_route("f16", M, N, K, need_dx=need_dx, need_dw=need_dw, need_db=need_db, dy_ld=dy.stride(0), x_ld=x.stride(0),
+                              aligned16=dy.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0)
     dx = dw = db = None
-    if need_dx:
+    if r.dx == "nt":
         if wT is None:
             wT = transpose16(w, 64)                       # [K, Npad]: reduction over N
         dyp = dy if N % 64 == 0 else torch.nn.functional.pad(dy, (0, wT.shape[1] - N))
         dx = torch.empty((M, K), dtype=dy.dtype, device=dev)
         gemm(dyp, wT, None, dx, EPI_STORE16)
-    if need_dw:
-        # reduction over the M rows: few output tiles, a very long K -> split it over workgroups (partial tiles + reduce kernel)
-        ks, unit = wgrad_ksplit(N, K, M)
+    # dw: a reduction over the M rows -- few output tiles, a very long K, split over workgroups (partial tiles + reduce kernel)
+    if r.wgrad is not None:
         dw = torch.empty((N, K), dtype=torch.float32, device=dev)
-        skinny = M >= 1 << 20                    # millions of rows: HBM-bound whatever the tile fill, and the transposes cost 3 passes
-        if (((N % 256 == 0 and K % 256 == 0) or skinny) and dy.stride(0) % 8 == 0 and x.stride(0) % 8 == 0
-                and dy.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0 and dy.stride(0) >= (N + 7) // 8 * 8):
-            # the reduction-major kernel reads dY and X as they are (LDS transpose reads), no transposed copies
-            gemm_wgrad_tn(dy, x, dw, ks if (N % 256 == 0 and K % 256 == 0) else max(1, min(256, M // 512)), accumulate=False)
-            if need_db:
-                if N % 8 == 0:
-                    db = colsum(dy)
-                else:                             # rows padded with zeros up to a multiple of 8 (gaussian_adapter_backward): 16-byte loads
-                    Np = (N + 7) // 8 * 8
-                    db = colsum(torch.as_strided(dy, (M, Np), (dy.stride(0), 1)))[:N].contiguous()
-        else:
-            if need_db:
-                db = torch.empty(N, dtype=torch.float32, device=dev)
-            # slice-blocked [ks, N, Mpad/ks], [ks, K, Mpad/ks], zero padded
-            dyT, xT = transpose16(dy, unit, colsum_out=db, slices=ks), transpose16(x, unit, slices=ks)
-            gemm_wgrad(dyT, xT, dw, ks, accumulate=False)
-    elif need_db:
+    if r.wgrad in ("tn256", "tn_skinny"):         # the reduction-major kernel reads dY and X as they are (LDS transpose reads), no transposed copies
+        gemm_wgrad_tn(dy, x, dw, r.ksplit, accumulate=False)
+    elif r.wgrad == "transposed":                 # slice-blocked [ks, N, pad/ks], [ks, K, pad/ks], zero padded
+        if r.db == "on_transpose":
+            db = torch.empty(N, dtype=torch.float32, device=dev)
+        dyT, xT = transpose16(dy, r.pad, colsum_out=db, slices=r.ksplit), transpose16(x, r.pad, slices=r.ksplit)
+        gemm_wgrad(dyT, xT, dw, r.ksplit, accumulate=False)
+    if r.db == "colsum":
         db = colsum(dy)
+    elif r.db == "colsum_padded":                 # rows padded with zeros up to a multiple of 8 (gaussian_adapter_backward): 16-byte loads
+        db = colsum(torch.as_strided(dy, (M, round_up(N, 8)), (dy.stride(0), 1)))[:N].contiguous()
     return dx, dw, db
 
 
@@ -879,8 +861,9 @@ def gemm_wgrad(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, ksplit: int,
 
 
 def gemm_wgrad_tn(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, ksplit: int, *, workspace: bool = True, accumulate: bool = True):
-    """out32[M,N] (+)= a^T @ w for reduction-major operands a [Kred, M], w [Kred, N] (16-bit, row stride any multiple of 8): the weight
-    gradient dW = dY^T X without transposed copies (vs_gemm_wgrad_tn; M, N multiples of 256)."""
+    """out32[M,N] (+)= a^T @ w for reduction-major operands a [Kred, M], w [Kred, N] (16-bit, 16-byte aligned, row strides multiples of 8 that
+    cover M / N): the weight gradient dW = dY^T X without transposed copies (vs_gemm_wgrad_tn).  Any M, N: 256 x 256 tiles, columns past the
+    rows' storage read as zeros; any Kred: the last of the ksplit slices is zero-filled.  accumulate=False needs the workspace."""
     dev = L.require_device(a, w, out)
     assert a.dtype == w.dtype and a.stride(1) == 1 and w.stride(1) == 1 and a.shape[0] == w.shape[0]
     assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (a.shape[1], w.shape[1])
@@ -910,8 +893,7 @@ def conv3x3_backward(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, *, relu
     dy [N,H,W,Cout], x [N,H,W,Cin] (the conv input, before the fused input ReLU), w [Cout,3,3,Cin], all 16-bit NHWC.
     Returns dx [N,H,W,Cin] 16-bit, dw [Cout,3,3,Cin] f32, db [Cout] f32.
       dx: the same implicit-GEMM kernel on dy with the spatially flipped, channel-transposed weights;
-      dw: per tap one split-K GEMM over the zero-bordered, transposed activations -- the tap shift is a column shift of the
-          [Cin, pixels] operand (LDS-DMA reads any 2-byte aligned address), so no im2col buffer exists here either."""
+      dw, db: the route conv3x3_backward_route names -- either way a tap is a shift of an operand, so no im2col buffer exists here either."""
     N, H, W, Cin = x.shape
     Cout = w.shape[0]
     dev, dt = x.device, x.dtype
@@ -919,40 +901,31 @@ def conv3x3_backward(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, *, relu
     if need_dx:
         wd = w.flip(1, 2).permute(3, 1, 2, 0).contiguous()          # [Cin, 3, 3, Cout]
         dx = conv3x3_nhwc(dy.contiguous(), wd, None, mask_by=x if relu_in else None)   # ReLU backward in the conv epilogue
-    r256 = lambda c: (c + 255) // 256 * 256
-    G = 256 // Cin if (Cin <= 128 and 256 % Cin == 0) else 1              # taps that share one 256-row tile (conv3x3_wgrad_tn_kernel)
-    groups = (9 + G - 1) // G
-    tile_rows = groups * 256 if G > 1 else 9 * r256(Cin)
-    if (Cin % 8 == 0 and Cout % 8 == 0 and 9 * Cin * Cout >= 0.4 * tile_rows * r256(Cout) and x.is_contiguous() and dy.is_contiguous()):
-        # 256 x 256 tiles at least 40 % full: the reduction-major kernel reads the NHWC tensors as they are (tap shift = pixel-row
-        # shift, zero page outside the image, input ReLU on the fragments) -- no zero-bordered transposed copies
-        P = N * H * W
-        ks, _ = wgrad_ksplit(256 if G > 1 else r256(Cin), r256(Cout), P, groups if G > 1 else 9)
+    r = conv3x3_backward_route("f16", N, H, W, Cin, Cout, contiguous=x.is_contiguous() and dy.is_contiguous(), need_dx=need_dx, need_db=need_db)
+    ks, P = r.ksplit, N * H * W
+    if r.wgrad in ("tn", "tn_grouped"):
+        # the reduction-major kernel reads the NHWC tensors as they are (tap shift = pixel-row shift, zero page outside the image, input
+        # ReLU on the fragments) -- no zero-bordered transposed copies
         dw9 = torch.empty((9, Cin, Cout), dtype=torch.float32, device=dev)
         ws = torch.empty(ks * 9 * Cin * Cout, dtype=torch.float32, device=dev)
         L.call("vs_conv3x3_wgrad_tn", dev, L.ptr(x), L.ptr(dy), L.ptr(dw9), N, H, W, Cin, Cout, int(relu_in), ks, _DT[dt], L.ptr(ws), ws.numel() * 4,
                0)
         dw = dw9.view(3, 3, Cin, Cout).permute(3, 0, 1, 2).contiguous()            # [Cout, ky, kx, Cin]
-        return dx, dw, (colsum(dy.view(P, Cout)) if need_db else None)
-    # weight gradient: dY^T [Cout, pixels] and X^T [Cin, pixels] over the zero-bordered pixel grid, produced straight from the
-    # NHWC tensors by the transposing kernel (border, input ReLU and the bias gradient folded into that one pass)
-    Hp, Wp = H + 2, W + 2
-    P = N * Hp * Wp
-    ksplit, unit = wgrad_ksplit(Cout, Cin, P, 9)
-    Ppad = (P + unit - 1) // unit * unit
-    halo = (Wp + 2 + 7) // 8 * 8                                    # >= largest |tap shift| + 1; keeps the rows 16-byte aligned
-    xT = transpose16(x.view(N * H * W, Cin), unit, border_hw=(H, W), relu=relu_in, slices=ksplit, halo=halo if ksplit > 1 else 0)
-    if ksplit == 1:                                                 # one slice: the shifted views need zero columns on either side
+        return dx, dw, (colsum(dy.view(P, Cout)) if r.db else None)
+    # transposed: dY^T [Cout, pixels] and X^T [Cin, pixels] over the zero-bordered pixel grid, produced straight from the NHWC
+    # tensors by the transposing kernel (border, input ReLU and the bias gradient folded into that one pass)
+    shifts, halo = bordered_taps(W, 8)
+    xT = transpose16(x.view(P, Cin), r.pad, border_hw=(H, W), relu=relu_in, slices=ks, halo=halo if ks > 1 else 0)
+    if ks == 1:     # whole 256-tiles of a small map that missed `tn` (a strided x or dy): one slice is a plain 2-D operand, its halo added here
         xT = torch.nn.functional.pad(xT, (halo, halo)).unsqueeze(0)
     db = torch.empty(Cout, dtype=torch.float32, device=dev)
-    dyT = transpose16(dy.contiguous().view(N * H * W, Cout), unit, colsum_out=db, border_hw=(H, W), slices=ksplit)
-    if ksplit == 1:
+    dyT = transpose16(dy.contiguous().view(P, Cout), r.pad, colsum_out=db, border_hw=(H, W), slices=ks)
+    if ks == 1:
         dyT = dyT.unsqueeze(0)
     # all 9 taps in ONE launch (workgroup order: k-slice, tap, tile): the taps of a K slice run together, so A and the nine
     # overlapping shifted views of X^T are served from the caches instead of being streamed from HBM nine times
     dw9 = torch.empty((9, Cout, Cin), dtype=torch.float32, device=dev)
-    shifts = [(ty - 1) * Wp + (tx - 1) for ty in range(3) for tx in range(3)]
-    gemm_wgrad(dyT, xT[:, :, halo:halo + Ppad // ksplit], dw9, ksplit, shifts=shifts, accumulate=False)
+    gemm_wgrad(dyT, xT[:, :, halo:halo + r.pad // ks], dw9, ks, shifts=shifts, accumulate=False)
     dw = dw9.view(3, 3, Cout, Cin).permute(2, 0, 1, 3).contiguous()
     return dx, dw, db
 
@@ -1074,72 +1047,54 @@ def gemm_wgrad_split_atn(a: torch.Tensor, w: SplitWeight, out: torch.Tensor, ksp
     return out
 
 
-def _wgrad_split(dyT: torch.Tensor, xT: SplitWeight, out: torch.Tensor) -> torch.Tensor:
-    M, N, K = dyT.shape[0], xT.shape[0], dyT.shape[1]
-    if M % 256 == 0 and N % 256 == 0:
-        tiles = (M // 256) * (N // 256)
-        ks = max(1, min((256 + tiles // 2) // tiles, K // 512))
-        while ks > 1 and K % (64 * ks) != 0:
-            ks -= 1
-    else:
-        tiles = ((M + 127) // 128) * ((N + 127) // 128)
-        ks = max(2, min(768 // tiles, K // 512, 1024))
-        while ks > 2 and K % (64 * ks) != 0:
-            ks -= 1
-    return gemm_wgrad_split(dyT, xT, out, ks)
+def _rows16_f32(t: torch.Tensor) -> torch.Tensor:
+    """t, or a contiguous copy where its f32 rows are not 16-byte aligned."""
+    return t if (t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0) else t.contiguous()
 
 
 def linear_backward_split(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, *, need_dx: bool = True, need_dw: bool = True, need_db: bool = True,
                           scale_exp: Optional[int] = None, dgelu_z: Optional[torch.Tensor] = None):
     """Backward of y = x @ w^T + b in the split class: dy [M,N], x [M,K], w [N,K] all f32 -> dx [M,K], dw [N,K], db [N] f32.
-    dx = vs_gemm_split(dy, pack(w^T)); dw = vs_gemm_wgrad(transpose(dy), transpose_pack(x)) over the M rows; db = column sums.
+    dx = vs_gemm_split(dy, pack(w^T)); dw = dy^T x over the M rows; db = column sums: each on the route linear_backward_route names.
     dgelu_z [M,K] f32 (x = gelu(z), the MLP's second linear): the returned dx is the gradient of z, dy w^T * GELU'(z), multiplied in the dX
     GEMM's epilogue (vs_gemm_split epilogue 5) instead of a separate pass over dx and z."""
     M, N = dy.shape
     K = x.shape[1]
     dev = dy.device
     assert dy.dtype == torch.float32 and x.dtype == torch.float32 and dy.stride(1) == 1 and x.stride(1) == 1
+    wf = w.detach().float() if need_dx else None
+    r = linear_backward_route("split", M, N, K, need_dx=need_dx, need_dw=need_dw, need_db=need_db, scale_exp_known=scale_exp is not None,
+                              w_contiguous=need_dx and wf.is_contiguous(),
+                              dgelu=None if dgelu_z is None else dgelu_z.shape == (M, K) and dgelu_z.is_contiguous() and dgelu_z.dtype == torch.float32)
     dx = dw = db = None
-    if need_dx:
-        wf = w.detach().float()
-        if N % 64 == 0 and scale_exp is not None and wf.is_contiguous():
-            dyp = dy if (dy.stride(0) % 4 == 0 and dy.data_ptr() % 16 == 0) else dy.contiguous()
-            wtp = transpose_pack_split(wf, 64, scale_exp=int(scale_exp))          # pack(w^T) in one pass: no transposed f32 copy of the weight
+    if r.dx == "pack_t":
+        dyp = _rows16_f32(dy)
+        wtp = transpose_pack_split(wf, 64, scale_exp=int(scale_exp))          # pack(w^T) in one pass: no transposed f32 copy of the weight
+    elif r.dx == "padded":
+        if N % 32 != 0:
+            wt, dyp = torch.nn.functional.pad(wf.t(), (0, (-N) % 32)), torch.nn.functional.pad(dy, (0, (-N) % 32))
         else:
-            wt = wf.t()
-            if N % 32 != 0:
-                wt = torch.nn.functional.pad(wt, (0, (-N) % 32))
-                dyp = torch.nn.functional.pad(dy, (0, (-N) % 32))
-            else:
-                dyp = dy if (dy.stride(0) % 4 == 0 and dy.data_ptr() % 16 == 0) else dy.contiguous()
-            wtp = split_pack_weight(wt.contiguous(), scale_exp)
+            wt, dyp = wf.t(), _rows16_f32(dy)
+        wtp = split_pack_weight(wt.contiguous(), scale_exp)
+    if r.dx is not None:
         dx = torch.empty((M, K), dtype=torch.float32, device=dev)
-        if dgelu_z is not None and dyp.shape[1] % 64 == 0 and dgelu_z.shape == dx.shape and dgelu_z.is_contiguous() and dgelu_z.dtype == torch.float32:
+        if r.dgelu == "epilogue":
             _gemm_split(dyp, wtp, None, dx, 5, resid=dgelu_z)
         else:
             _gemm_split(dyp, wtp, None, dx, EPI_STORE32)
-            if dgelu_z is not None:
+            if r.dgelu == "pass":
                 dx = gelu_backward(dx, dgelu_z.contiguous())
-    if need_dw:
-        Mp = (M + 1023) // 1024 * 1024 if M >= 4096 else (M + 127) // 128 * 128      # (room for the K split; zero rows cost nothing exact)
-        dys = dy if (dy.stride(0) % 4 == 0 and dy.data_ptr() % 16 == 0) else dy.contiguous()
-        xs = x if (x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0) else x.contiguous()
-        if need_db:
-            db = torch.empty(N, dtype=torch.float32, device=dev)          # the bias gradient rides on the transpose of dY
+    if r.wgrad is not None:
+        dys, xs = _rows16_f32(dy), _rows16_f32(x)
+        if r.db == "on_transpose":
+            db = torch.empty(N, dtype=torch.float32, device=dev)
         dw = torch.empty((N, K), dtype=torch.float32, device=dev)
-        if N % 256 == 0 and K % 256 == 0:
-            # dW^T [K, N] = X^T dY with X read as it is (reduction-major A operand); only dY goes through a transposing (packing) pass
-            dyTp = transpose_pack_split(dys, Mp, colsum=db)               # [N, Mp] packed
-            tiles = (N // 256) * (K // 256)
-            ks = max(1, min((256 + tiles // 2) // tiles, Mp // 512))
-            while ks > 1 and Mp % (64 * ks) != 0:
-                ks -= 1
-            gemm_wgrad_split_atn(xs, dyTp, dw, ks, transpose_out=True)
-        else:
-            dyT = transpose_f32(dys, Mp, colsum=db)      # [N, Mp]
-            xT = transpose_pack_split(xs, Mp)            # [K, Mp] packed
-            _wgrad_split(dyT, xT, dw)
-    if need_db and db is None:
+    if r.wgrad == "atn256":         # dW^T [K, N] = X^T dY with X read as it is (reduction-major A operand); only dY goes through a transposing (packing) pass
+        gemm_wgrad_split_atn(xs, transpose_pack_split(dys, r.pad, colsum=db), dw, r.ksplit, transpose_out=True)      # dY^T [N, pad] packed
+    elif r.wgrad == "transposed":
+        dyT = transpose_f32(dys, r.pad, colsum=db)      # [N, pad]
+        gemm_wgrad_split(dyT, transpose_pack_split(xs, r.pad), dw, r.ksplit)      # X^T [K, pad] packed
+    if r.db == "colsum":
         db = colsum(dy)
     return dx, dw, db
 
@@ -1173,6 +1128,7 @@ def head1x1_backward(dy: torch.Tensor, t: torch.Tensor, w: torch.Tensor, *, relu
 
 
 def head1x1_backward_split(dy, t, w, *, relu: bool = True, scale_exp: int = 0):
+    """head1x1_backward held to the split class: the name tests/test_split_bwd_gpu.py runs vs_head1x1_backward_split under."""
     assert dy.dtype == torch.float32
     return head1x1_backward(dy, t, w, relu=relu, scale_exp=scale_exp)
 
@@ -1188,7 +1144,7 @@ def attention_backward_split(qkv_q: torch.Tensor, qkv_k: torch.Tensor, qkv_v: to
     Cc = H * 64
     for t in (qkv_q, qkv_k, qkv_v, out, dout):
         assert t.dim() == 2 and t.stride(1) == 1 and t.dtype == torch.float32 and t.shape[1] == Cc
-    dout = dout if (dout.stride(0) % 4 == 0 and dout.data_ptr() % 16 == 0) else dout.contiguous()
+    dout = _rows16_f32(dout)
     qh, ql = split16(qkv_q)
     kh, kl = split16(qkv_k)
     vh, vl = split16(qkv_v)
@@ -1232,8 +1188,7 @@ def conv3x3_backward_split(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, *
     """Backward of conv3x3_nhwc(x, pack(w), relu_in=relu_in) (stride 1, pad 1) in the split class.  dy [N,H,W,Cout], x [N,H,W,Cin] f32 NHWC,
     w the module's [Cout,Cin,3,3] f32 parameter -> dx [N,H,W,Cin], dw [Cout,Cin,3,3], db [Cout], all f32.
       dx: the forward kernel on the spatially flipped, channel-transposed weights (ReLU backward in its epilogue);
-      dw: per tap one weight-gradient GEMM dY^T [Cout, pixels] x act(X shifted by the tap)^T [Cin, pixels] -- the shifted operand is
-          written by the transposing pack kernel (zero outside the image), so no im2col buffer and no zero-bordered copy exists."""
+      dw, db: the route conv3x3_backward_route names; no im2col buffer on any of them."""
     N, H, W, Cin = x.shape
     Cout = w.shape[0]
     dev = x.device
@@ -1248,44 +1203,31 @@ def conv3x3_backward_split(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, *
             dyp = torch.nn.functional.pad(dy, (0, pad_o))
         wdp = split_pack_weight(wd, scale_exp)
         dx = conv3x3_nhwc(dyp, wdp, None, mask_by=x if relu_in else None)
-    # weight gradient: ONE tap-fused launch over the zero-bordered pixel grid.  A = act(X)^T [Cin, pixels] f32 with a zero halo (the nine tap
-    # shifts are column offsets of this operand: LDS-DMA reads any 4-byte aligned f32 address), W = dY^T [Cout, pixels] packed (hi, lo);
-    # out[tap] = [Cin, Cout].  Two transposing passes instead of nine packed shifted images.
+    r = conv3x3_backward_route("split", N, H, W, Cin, Cout, need_dx=need_dx, need_db=need_db)
     P = N * H * W
-    if Cin % 256 == 0 and Cout % 256 == 0:
-        # X read as it is by the reduction-major A operand (tap shift = pixel-row shift, zero page outside the image): only dY goes through a
-        # transposing (packing) pass, which also yields the bias gradient
-        tiles = (Cin // 256) * (Cout // 256) * 9
-        ks = max(1, min((256 + tiles // 2) // tiles, P // 512))
-        db = torch.empty(Cout, dtype=torch.float32, device=dev) if need_db else None
-        dyTp = transpose_pack_split(dy.view(P, Cout), 64 * ks, colsum=db)                                   # [Cout, Ppad] packed
-        dw9 = torch.empty((9, Cin, Cout), dtype=torch.float32, device=dev)
-        ws = torch.empty(ks * 9 * Cin * Cout, dtype=torch.float32, device=dev)
-        L.call("vs_conv3x3_wgrad_split_atn", dev, L.ptr(x), L.ptr(dyTp.data), L.ptr(dw9), N, H, W, Cin, Cout, dyTp.data.shape[1], dyTp.data.stride(0),
-               int(relu_in), ks, L.ptr(ws), ws.numel() * 4, 0)
-        return dx, dw9.view(3, 3, Cin, Cout).permute(3, 2, 0, 1).contiguous(), db
-    if Cin % 64 == 0 and Cout % 64 == 0 and W % 32 == 0:
-        # narrow layers (the pts3d head's 256 -> 128 and 128 -> 128 convolutions): one streaming pass over X and dY as they are
-        # (csrc/conv_wgrad_stream.hip) instead of two transposing passes + nine 128 x 128 tiles per K slice on the 4-wave kernel
+    if r.wgrad == "stream":
+        # one streaming pass over X and dY as they are (csrc/conv_wgrad_stream.hip) instead of two transposing passes + nine 128 x 128
+        # tiles per K slice on the 4-wave kernel
         dw9, db = conv3x3_wgrad_split_stream(dy, x, relu_in=relu_in)
-        return dx, dw9.view(3, 3, Cin, Cout).permute(3, 2, 0, 1).contiguous(), (db if need_db else None)
-    Wp = W + 2
-    Pb = N * (H + 2) * Wp
-    tiles = ((Cin + 255) // 256) * ((Cout + 255) // 256) * 9 if (Cin % 256 == 0 and Cout % 256 == 0) else ((Cin + 127) // 128) * ((Cout + 127) // 128) * 9
-    if Cin % 256 == 0 and Cout % 256 == 0:
-        ks = max(1, min((256 + tiles // 2) // tiles, Pb // 512))
-    else:
-        ks = max(2, min(768 // tiles, Pb // 512, 1024))
-    unit = 64 * ks * (2 if (Cin % 256 == 0 and Cout % 256 == 0) else 1)
-    halo = (Wp + 2 + 3) // 4 * 4
-    xT = transpose_f32(x.view(P, Cin), unit, relu=relu_in, conv_hw=(H, W), border=True, halo=halo)          # [Cin, Pp] view of the haloed buffer
-    db = torch.empty(Cout, dtype=torch.float32, device=dev) if need_db else None                            # (rides on the transpose of dY)
-    dyT = transpose_pack_split(dy.view(P, Cout), unit, conv_hw=(H, W), border=True, colsum=db)              # [Cout, Pp] packed
+        return dx, dw9.view(3, 3, Cin, Cout).permute(3, 2, 0, 1).contiguous(), (db if r.db else None)
+    db = torch.empty(Cout, dtype=torch.float32, device=dev) if r.db else None      # (rides on the transpose of dY)
     dw9 = torch.empty((9, Cin, Cout), dtype=torch.float32, device=dev)
-    shifts = [(ty - 1) * Wp + (tx - 1) for ty in range(3) for tx in range(3)]
-    gemm_wgrad_split(xT, dyT, dw9, ks, shifts=shifts)
-    dw = dw9.view(3, 3, Cin, Cout).permute(3, 2, 0, 1).contiguous()                                          # [Cout, Cin, ky, kx]
-    return dx, dw, db
+    if r.wgrad == "atn256":
+        # X read as it is by the reduction-major A operand (tap shift = pixel-row shift, zero page outside the image): only dY goes through a
+        # transposing (packing) pass
+        dyTp = transpose_pack_split(dy.view(P, Cout), r.pad, colsum=db)                                     # [Cout, pad] packed
+        ws = torch.empty(r.ksplit * 9 * Cin * Cout, dtype=torch.float32, device=dev)
+        L.call("vs_conv3x3_wgrad_split_atn", dev, L.ptr(x), L.ptr(dyTp.data), L.ptr(dw9), N, H, W, Cin, Cout, dyTp.data.shape[1], dyTp.data.stride(0),
+               int(relu_in), r.ksplit, L.ptr(ws), ws.numel() * 4, 0)
+    else:
+        # transposed: ONE tap-fused launch over the zero-bordered pixel grid.  A = act(X)^T [Cin, pixels] f32 with a zero halo (the nine tap
+        # shifts are column offsets of this operand: LDS-DMA reads any 4-byte aligned f32 address), W = dY^T [Cout, pixels] packed (hi, lo);
+        # out[tap] = [Cin, Cout].  Two transposing passes instead of nine packed shifted images.
+        shifts, halo = bordered_taps(W, 4)
+        xT = transpose_f32(x.view(P, Cin), r.pad, relu=relu_in, conv_hw=(H, W), border=True, halo=halo)     # [Cin, pad] view of the haloed buffer
+        dyT = transpose_pack_split(dy.view(P, Cout), r.pad, conv_hw=(H, W), border=True, colsum=db)         # [Cout, pad] packed
+        gemm_wgrad_split(xT, dyT, dw9, r.ksplit, shifts=shifts)
+    return dx, dw9.view(3, 3, Cin, Cout).permute(3, 2, 0, 1).contiguous(), db                               # [Cout, Cin, ky, kx]
 
 
 def sustained_mfma_tflops(device, ms_target: float = 40.0) -> float:
