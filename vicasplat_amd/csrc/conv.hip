@@ -38,9 +38,11 @@ struct ConvArgs {
 
 // epilogue shared by the conv kernels (accumulators are C^T, see gemm_common.h: a lane holds 4 consecutive output
 // channels of one pixel per fragment): + bias, + residual (8-byte load, added in f32), ReLU, round to 16 bit, one 8-byte
-// store per fragment -- no LDS round trip.  mw0 / nbase = first output pixel / channel of the wave's tile.
+// store per fragment -- no LDS round trip.  mw0 / nbase = first output pixel / channel of the wave's tile.  istep = pixels between the row
+// fragments of the wave (f32 activations only): 16 for a tile of consecutive pixels, W for the halo kernel's 16-pixel runs of consecutive image rows.
 template <int BF16, int MI>
-__device__ __forceinline__ void conv_epilogue(const ConvArgs &g, f4 (&acc)[MI][4], int mw0, int nbase, int M, void *, int, int lane) {
+__device__ __forceinline__ void conv_epilogue(const ConvArgs &g, f4 (&acc)[MI][4], int mw0, int nbase, int M, void *, int, int lane,
+                                              const int istep = 16) {
     const int mrow = lane & 15, c4 = (lane >> 4) * 4;
     if constexpr (BF16 == kDtSplit) {
 #pragma unroll
@@ -111,13 +113,13 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs &g, f4 (&acc)[MI][4
     }
     // f32 activations (f32 / split operand classes), interior wave tile: 16-byte residual loads and output stores, straight-line
     if constexpr (is_f32io(BF16)) {
-        if (g.Cout % 4 == 0 && nbase + 64 <= g.Cout && mw0 + 16 * MI <= M &&
+        if (g.Cout % 4 == 0 && nbase + 64 <= g.Cout && mw0 + (MI - 1) * istep + 16 <= M &&
             ((reinterpret_cast<uintptr_t>(g.out) | reinterpret_cast<uintptr_t>(g.res) | reinterpret_cast<uintptr_t>(g.res2)) & 15) == 0) {
             const float *res32 = reinterpret_cast<const float *>(g.res);
             float *out32 = reinterpret_cast<float *>(g.out);
 #pragma unroll
             for (int i = 0; i < MI; ++i) {
-                const size_t o = (size_t)(mw0 + i * 16 + mrow) * g.Cout + nbase + c4;
+                const size_t o = (size_t)(mw0 + i * istep + mrow) * g.Cout + nbase + c4;
                 float4 rv[4];
                 if (res32) {
 #pragma unroll
@@ -149,7 +151,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs &g, f4 (&acc)[MI][4
     }
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
-        const int m = mw0 + i * 16 + mrow;
+        const int m = mw0 + i * (is_f32io(BF16) ? istep : 16) + mrow;
         if (m >= M) continue;
         const size_t o = (size_t)m * g.Cout + nbase + c4;
 #pragma unroll
@@ -507,6 +509,79 @@ __global__ void __launch_bounds__(512, 1) conv3x3_256_kernel(const ConvArgs g, c
     if constexpr (FUSE_NF > 0 && BF16 == kDtSplit) conv_head1x1_split_epilogue256<FUSE_NF>(g, acc, m0, wr, wc, smem, wid, lane);
     else if constexpr (FUSE_NF > 0) conv_head1x1_epilogue256<BF16, FUSE_NF>(g, acc, m0, wr, wc, smem, wid, lane);
     else conv_epilogue<BF16, 8>(g, acc, m0 + wr * 128, n0 + wc * 64, M, smem, wid, lane);
+}
+
+// ---- halo-tile variant of the split-class kernel above (gemm256.h, mainloop256_halo_split): stride 1, f32 NHWC input, Cout = 256, H and W
+// multiples of 16 (other sizes keep conv3x3_256_kernel: no partial patches).  A workgroup owns a 16 x 16 block of output pixels of one image
+// and stages + converts the 18 x 18 input patch ONCE per 32-channel block where the kernel above staged and converted the 256 tap-shifted
+// rows nine times; same K order, so the same bits. ----
+struct ConvHaloStager {
+    // 32-bit element offsets from workgroup-uniform bases (the image, the weights): the loop has no VGPRs to spare for 64-bit pointers
+    const unsigned short *img;       // pixel (0, 0), channel 0 of this workgroup's image
+    const unsigned short *wgt;
+    unsigned po[3][2];               // [item round][instruction]: this lane's 16 bytes of its patch row in channel block 0
+    unsigned pmask;                  // bit 2 r + k: po[r][k] is a pixel inside the image; the zero page otherwise
+    unsigned wo;                     // this lane's 16 bytes of weight row unit_b_tile_row256(q, 0), round 0; B_h / round j: + (32 h + 8 j) rows
+    int K, kpt;                      // weight row length; channel blocks (the weight rows stay [tap][channel])
+    int zo;                          // this lane's 16 bytes of the zero page
+    __device__ __forceinline__ void stage_p(int r, int cb, unsigned lds) const {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const bool ok = (pmask >> (2 * r + k)) & 1u;
+            glds16(ok ? img + (po[r][k] + (unsigned)(cb * 64)) : vs_zero_page + zo, lds + k * 1024u);
+        }
+    }
+    __device__ __forceinline__ void stage_b(int h, int tap, int cb, unsigned lds) const {
+        const unsigned short *w0 = wgt + ((size_t)(32 * h) * K + (tap * kpt + cb) * 64);    // wave-uniform
+        glds16(w0 + wo, lds);
+        glds16(w0 + (size_t)8 * K + (wo ^ 32u), lds + 1024u);     // (row q + 8 swizzles its chunks with the other value of bit 2; K % 64 == 0)
+    }
+};
+
+template <bool RELU_IN>
+__global__ void __launch_bounds__(512, 1) conv3x3_256_halo_split_kernel(const ConvArgs g, const int kpt) {
+    __shared__ __attribute__((aligned(1024))) unsigned char smem[kLdsBytesHalo];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wr = wid >> 2, wc = wid & 3;
+    const int K = 9 * g.Cin;
+    const int tiles_x = g.W >> 4, tiles_img = (g.H >> 4) * tiles_x;
+    const int nwg = g.Nimg * tiles_img;
+    int bid = blockIdx.x;
+    {
+        const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, idx = bid / 8;
+        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    }
+    const int nimg = bid / tiles_img, trem = bid - nimg * tiles_img;
+    const int y0 = (trem / tiles_x) * 16, x0 = (trem % tiles_x) * 16;
+
+    ConvHaloStager st;
+    st.K = K; st.kpt = kpt;
+    st.img = g.in + (size_t)nimg * g.H * g.W * g.Cin;
+    st.wgt = g.w;
+    st.zo = (lane & 7) * 8;
+    st.pmask = 0;
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int p = (r * 8 + wid) * 16 + k * 8 + (lane >> 3);        // patch row (rows >= 324 pad the last item)
+            const int chunk = (lane & 7) ^ ((p >> 1) & 7);
+            const int ry = p / 18, rx = p - ry * 18;
+            const int y = y0 - 1 + ry, x = x0 - 1 + rx;
+            const bool ok = p < 324 && (unsigned)y < (unsigned)g.H && (unsigned)x < (unsigned)g.W;
+            st.po[r][k] = ok ? (unsigned)((y * g.W + x) * g.Cin + chunk * 8) : 0u;      // (the entry keeps H * W * Cin below 2^31)
+            if (ok) st.pmask |= 1u << (2 * r + k);
+        }
+    {
+        // rows q and q + 8 of a B unit (rounds 0 / 1) are weight rows 8 apart, units B_0 / B_1 32 apart (unit_b_tile_row256)
+        const int q = unit_row256(wid, 0, lane);
+        st.wo = (unsigned)(unit_b_tile_row256(q, 0) * K + unit_src_chunk256(q, lane) * 8);
+    }
+    f4 acc[8][4];
+    mainloop256_halo_split<RELU_IN>(st, kpt, acc, smem, lane, wid);
+    // the wave's fragment i is the 16 pixels from x0 of image row y0 + wr * 8 + i
+    conv_epilogue<kDtSplit, 8>(g, acc, (nimg * g.H + y0 + wr * 8) * g.W + x0, wc * 64, g.Nimg * g.H * g.W, smem, wid, lane, g.W);
 }
 
 // ---- 256 x 128 tile on the split main loop (gemm256.h, mainloop256x128_split): the Cout = 128 layers of the pts3d head (conv 256 -> 128
@@ -1073,9 +1148,13 @@ static int conv3x3_entry(const void *in, const void *w, const float *bias, const
     // >= 150 tiles (round 5; was 224): a 59 %-full round of 256 x 256 tiles beats the 4-wave kernel's one and a half rounds at two workgroups
     // per CU in the split class (16 x 16 maps of the bench step: 0.21 -> 0.17 ms per convolution); 8 x 8 maps (48 tiles) stay where they were
     const long long t256_min = dtype == 4 ? 150 : 224;
+    // the halo-tile body of the split-class 256-wide route (conv3x3_256_halo_split_kernel), for the shapes it covers; M / 256 tiles either way
+    const bool halo = dtype == 4 && stride == 1 && Cout == 256 && H % 16 == 0 && W % 16 == 0 && !g.a_packed && (long long)H * W * Cin < 2147483647LL;
     if (dtype == 4 && cshift < 0 && kpt_any > 0 && Cout % 256 == 0 && (9 * kpt_any) % 2 == 0 && t256 >= t256_min && !g.a_packed) {
         dim3 grid((unsigned)t256), block(512);
-        if (relu_in) hipLaunchKernelGGL((conv3x3_256_kernel<kDtSplit, true>), grid, block, 0, stream, g, kpt_any);
+        if (halo && relu_in) hipLaunchKernelGGL((conv3x3_256_halo_split_kernel<true>), grid, block, 0, stream, g, kpt_any);
+        else if (halo) hipLaunchKernelGGL((conv3x3_256_halo_split_kernel<false>), grid, block, 0, stream, g, kpt_any);
+        else if (relu_in) hipLaunchKernelGGL((conv3x3_256_kernel<kDtSplit, true>), grid, block, 0, stream, g, kpt_any);
         else hipLaunchKernelGGL((conv3x3_256_kernel<kDtSplit, false>), grid, block, 0, stream, g, kpt_any);
         VS_HIP(hipGetLastError());
         return 0;
@@ -1084,6 +1163,8 @@ static int conv3x3_entry(const void *in, const void *w, const float *bias, const
         dim3 grid((unsigned)t256), block(512);
         if (dtype == 4) {
             if (g.a_packed) hipLaunchKernelGGL((conv3x3_256_kernel<kDtSplit, false, 0, true>), grid, block, 0, stream, g, 1 << cshift);
+            else if (halo && relu_in) hipLaunchKernelGGL((conv3x3_256_halo_split_kernel<true>), grid, block, 0, stream, g, 1 << cshift);
+            else if (halo) hipLaunchKernelGGL((conv3x3_256_halo_split_kernel<false>), grid, block, 0, stream, g, 1 << cshift);
             else if (relu_in) hipLaunchKernelGGL((conv3x3_256_kernel<kDtSplit, true>), grid, block, 0, stream, g, 1 << cshift);
             else hipLaunchKernelGGL((conv3x3_256_kernel<kDtSplit, false>), grid, block, 0, stream, g, 1 << cshift);
         } else if (dtype == 3) {

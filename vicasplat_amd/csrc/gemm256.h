@@ -357,6 +357,172 @@ __device__ __forceinline__ void mainloop256_split(Stager &st, const int KT, f4 (
     __syncthreads();  // every wave is done with the ring before an epilogue reuses it
 }
 
+// ---- halo-tile main loop of the split-class 3x3 convolution (stride 1, pad 1, f32 NHWC input, Cout tile 256): the M tile is a 16 x 16 block
+// of output pixels of ONE image, and per 32-channel block the A operand is the 18 x 18 input patch (the block plus a one-pixel halo), staged
+// and converted ONCE; the nine taps read it at shifted rows.  mainloop256_split stages and converts the 256 tap-shifted rows again for every
+// tap: 9 x 256 rows per channel block for 324 distinct ones.  Same 2 x 4 wave layout, acc[8][4], B units, phases, MFMA order inside a K-tile and
+// K order (channel block outermost, taps inside) as mainloop256_split with ConvStager256: every output is the same sum in the same order.
+// LDS: [patch 0][patch 1][dump][B ring: 2 slots x (B_0, B_1)].  A patch is 336 rows x 128 B (324 used) = 21 ITEMS of 16 rows; patch row
+// p = ry * 18 + rx holds pixel (y0 - 1 + ry, x0 - 1 + rx), zero outside the image (zero page on the source side: no out-of-range address is
+// formed).  The 16-byte chunk index is XORed with (p >> 1) & 7 on the source side and on every read: the A fragment of tap (ty, tx) for patch
+// row py is the 16 CONSECUTIVE rows from (py + ty) * 18 + tx, and 16 consecutive rows from ANY start hold, per row parity (the 128-byte rows
+// alternate between the two halves of the 64 banks), eight consecutive values of p >> 1 -- distinct mod 8, so the 16 lanes of a ds_read_b128
+// service group hit 16 distinct slots as in the aligned case.
+// Item m = r * 8 + wid (r = 0..2) is staged (two LDS-DMA instructions of 8 rows) and converted in place (split8_lds, with the ReLU) by wave wid
+// alone: a wave converts what it staged itself after its own vmcnt wait, no barrier in between.  Items 21..23 do not exist: their waves
+// stage the zero page into the dump, so that every wave issues the same number of loads and the vmcnt counts below are the same for all.
+// Per tap (K-tile kt, ring slot kt & 1), the wave groups one barrier apart as in mainloop256_split:
+//     R0: read B_0, A_0 | M0 (A0,B0) | R1: read B_1; stage B_0 of kt+2 | M1 (A0,B1) | R2: read A_1; stage B_1 of kt+2 | M2 (A1,B1)
+//     R3: [convert item t-2 of the NEXT patch]; [stage item t of the next patch]; wait | M3 (A1,B0)
+// The next channel block's patch is staged in R3 of taps 0, 1, 2 and converted in R3 of taps 2, 3, 4 (its buffer was last read nine taps
+// ago).  ONE wait per tap, in the barrier interval of group 0's M3 / group 1's R3: all but the loads issued in this tap (B_0, B_1 of kt+2 and
+// the tap's patch item) have landed -- B of kt+1 one barrier before its first read (R0 of kt+1), a patch item before its conversion two
+// taps later.  The conversion stores are in LDS (lgkmcnt 0) before the closing barrier of M3.
+constexpr unsigned kHaloPatchBytes = 336 * 128;
+constexpr unsigned kHaloDumpOff = 2 * kHaloPatchBytes;
+constexpr unsigned kHaloRingOff = kHaloDumpOff + 2048;
+constexpr unsigned kLdsBytesHalo = kHaloRingOff + 4 * kUnitBytes256;   // 150 KiB of the 160
+static_assert(kHaloRingOff % 1024 == 0, "units are 1 KiB-aligned");
+
+// `st.stage_b(h, tap, cb, lds)`: this wave's two loads of weight unit B_h of (channel block cb, tap); `st.stage_p(r, cb, lds)`: its two loads of
+// patch item r * 8 + wid of channel block cb.  NCB = channel blocks (>= 1).
+template <bool RELU_A, class Stager>
+__device__ __forceinline__ void mainloop256_halo_split(Stager &st, const int NCB, f4 (&acc)[8][4], unsigned char *smem, const int lane, const int wid) {
+    constexpr unsigned UNITB = kUnitBytes256;
+    constexpr int BF16 = kDtSplit;
+    const int wr = wid >> 2, wc = wid & 3;
+    typedef void __attribute__((address_space(3))) *lptr_t;
+    const unsigned lds0 = (unsigned)(size_t)(lptr_t)smem;
+    const unsigned lds_u = __builtin_amdgcn_readfirstlane(lds0);
+    const unsigned lds_w = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)wid * 2048u);
+    const int frow = lane & 15, fg = lane >> 4;
+    const unsigned rd0 = (unsigned)(frow * 128 + (((0 + fg) ^ (frow >> 1)) << 4));
+    const unsigned rd1 = (unsigned)(frow * 128 + (((4 + fg) ^ (frow >> 1)) << 4));
+    const unsigned char *rdB = smem + kHaloRingOff + wc * (32 * 128);
+    unsigned q0 = (unsigned)(wr * 8 * 18 + frow);       // patch row of this lane's pixel in fragment 0 of the wave, tap (0, 0)
+    // conversion item: rows in the order even, then odd (bank conflicts of the in-place ds_write_b128: see mainloop256_split)
+    const int crow = 2 * (frow & 7) + (frow >> 3);
+    const unsigned cv0 = (unsigned)(crow * 128 + (((0 + fg) ^ (crow >> 1)) << 4));
+    const unsigned cv1 = cv0 ^ 64u;
+    uint4 fa[4][2], fb[2][2][2], cx0, cx1;
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+
+    // patch item r of this wave in the patch buffer at byte offset pb_: LDS-DMA destination (dump for the items that do not exist) ...
+#define VS_STAGE_P(r_, cb_, pb_) st.stage_p(r_, cb_, ((r_) * 8 + wid < 21) ? lds_u + (pb_) + (unsigned)(((r_) * 8 + wid) * 2048) : lds_u + kHaloDumpOff);
+    // ... and its conversion, in place
+#define VS_CVT_P(r_, pb_)                                                                                        \
+    if ((r_) * 8 + wid < 21) {                                                                                   \
+        unsigned char *cp_ = smem + (pb_) + ((r_) * 8 + wid) * 2048;                                             \
+        cx0 = *reinterpret_cast<const uint4 *>(cp_ + cv0);                                                       \
+        cx1 = *reinterpret_cast<const uint4 *>(cp_ + cv1);                                                       \
+        if constexpr (RELU_A) {                                                                                  \
+            cx0.x = relu_f32_lds(cx0.x); cx0.y = relu_f32_lds(cx0.y); cx0.z = relu_f32_lds(cx0.z); cx0.w = relu_f32_lds(cx0.w); \
+            cx1.x = relu_f32_lds(cx1.x); cx1.y = relu_f32_lds(cx1.y); cx1.z = relu_f32_lds(cx1.z); cx1.w = relu_f32_lds(cx1.w); \
+        }                                                                                                        \
+        split8_lds(cx0, cx1);                                                                                    \
+        *reinterpret_cast<uint4 *>(cp_ + cv0) = cx0;                                                             \
+        *reinterpret_cast<uint4 *>(cp_ + cv1) = cx1;                                                             \
+    }
+    // B unit h of (channel block cb_, tap t_) into ring slot d_
+#define VS_STAGE_B(h_, t_, cb_, d_) st.stage_b(h_, t_, cb_, lds_w + kHaloRingOff + (unsigned)(((d_) * 2 + (h_)) * UNITB));
+#define VS_RD_A(h_, t_, pb_)                                                                                     \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                              \
+        const unsigned p_ = q0 + (unsigned)(((h_) * 4 + i + (t_) / 3) * 18 + (t_) % 3);                          \
+        const unsigned a_ = (pb_) + p_ * 128u + ((((p_ >> 1) ^ (unsigned)fg) & 7u) << 4);                        \
+        fa[i][0] = *reinterpret_cast<const uint4 *>(smem + a_);                                                  \
+        fa[i][1] = *reinterpret_cast<const uint4 *>(smem + (a_ ^ 64u));                                          \
+    }
+#define VS_RD_B(h_, d_)                                                                                          \
+    _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                              \
+        fb[h_][j][0] = *reinterpret_cast<const uint4 *>(rdB + ((d_) * 2 + (h_)) * UNITB + j * 2048 + rd0);       \
+        fb[h_][j][1] = *reinterpret_cast<const uint4 *>(rdB + ((d_) * 2 + (h_)) * UNITB + j * 2048 + rd1);       \
+    }
+#define VS_LGK0 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#define VS_MM(ha_, hb_)                                                                                          \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                \
+        _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                            \
+            acc[(ha_) * 4 + i][(hb_) * 2 + j] = mma2<BF16>(fb[hb_][j][0], fb[hb_][j][1], fa[i][0], fa[i][1], acc[(ha_) * 4 + i][(hb_) * 2 + j]);
+#define VS_BAR()                                  \
+    {                                             \
+        asm volatile("" ::: "memory");            \
+        __builtin_amdgcn_sched_barrier(0);        \
+        __builtin_amdgcn_s_barrier();             \
+        __builtin_amdgcn_sched_barrier(0);        \
+        asm volatile("" ::: "memory");            \
+    }
+#define VS_WAIT(n_) asm volatile("s_waitcnt vmcnt(" #n_ ")" ::: "memory");
+#define VS_COMPUTE(ha_, hb_, g0_wait_, all_wait_) \
+    {                                             \
+        VS_BAR()                                  \
+        __builtin_amdgcn_s_setprio(1);            \
+        VS_MM(ha_, hb_)                           \
+        __builtin_amdgcn_s_setprio(0);            \
+        if (wr == 0) { g0_wait_ }                 \
+        all_wait_                                 \
+        VS_BAR()                                  \
+    }
+    // the tap's one wait: MORE_ = B of kt+2 is staged in this tap, PST_ = so is a patch item
+#define VS_TAPWAIT(MORE_, PST_) { if (MORE_) { if (PST_) { VS_WAIT(6) } else { VS_WAIT(4) } } else { VS_WAIT(0) } }
+    // tap t_ of channel block cb (runtime), LAST_ = the last channel block; pc / pn = byte offsets of the current / next patch buffer, ring slot
+    // d_ = (9 cb + t_) & 1.  B of kt+2 is tap t_+2 of this block or tap t_-7 of the next.
+#define VS_TAP(t_, LAST_)                                                         \
+    {                                                                             \
+        const int d_ = (cb + (t_)) & 1;                                           \
+        constexpr bool more_ = !(LAST_) || (t_) + 2 < 9;                          \
+        constexpr bool pst_ = !(LAST_) && (t_) < 3;                               \
+        constexpr int t2_ = (t_) + 2 < 9 ? (t_) + 2 : (t_) - 7;                   \
+        const int cb2_ = (t_) + 2 < 9 ? cb : cb + 1;                              \
+        asm volatile("" : "+v"(q0));   /* (opaque: the 72 fragment addresses of a block are recomputed per tap, not kept in registers) */ \
+        VS_RD_B(0, d_) VS_RD_A(0, t_, pc)                                         \
+        VS_COMPUTE(0, 0, , )                                                      \
+        VS_RD_B(1, d_)                                                            \
+        if constexpr (more_) VS_STAGE_B(0, t2_, cb2_, d_)                         \
+        VS_COMPUTE(0, 1, , )                                                      \
+        VS_RD_A(1, t_, pc)                                                        \
+        if constexpr (more_) VS_STAGE_B(1, t2_, cb2_, d_)                         \
+        VS_COMPUTE(1, 1, , )                                                      \
+        if constexpr (!(LAST_) && (t_) >= 2 && (t_) < 5) VS_CVT_P((t_) - 2, pn)   \
+        if constexpr (pst_) VS_STAGE_P(t_, cb + 1, pn)                            \
+        if (wr == 1) VS_TAPWAIT(more_, pst_)                                      \
+        VS_COMPUTE(1, 0, VS_TAPWAIT(more_, pst_), VS_LGK0)                        \
+    }
+#define VS_BLOCK(LAST_) { VS_TAP(0, LAST_) VS_TAP(1, LAST_) VS_TAP(2, LAST_) VS_TAP(3, LAST_) VS_TAP(4, LAST_) VS_TAP(5, LAST_) VS_TAP(6, LAST_) VS_TAP(7, LAST_) VS_TAP(8, LAST_) }
+
+    // Prologue: the whole patch of block 0, B of taps 0 and 1; the patch converted by its owners before the first fragment read.
+    int cb = 0;
+    unsigned pc = 0, pn = kHaloPatchBytes;
+    VS_STAGE_P(0, 0, pc) VS_STAGE_P(1, 0, pc) VS_STAGE_P(2, 0, pc)
+    VS_STAGE_B(0, 0, 0, 0) VS_STAGE_B(1, 0, 0, 0) VS_STAGE_B(0, 1, 0, 1) VS_STAGE_B(1, 1, 0, 1)
+    VS_WAIT(4)
+    VS_CVT_P(0, pc) VS_CVT_P(1, pc) VS_CVT_P(2, pc)
+    VS_LGK0
+    VS_BAR()
+    if (wr == 1) VS_BAR()  // the second wave group trails the first by one barrier from here on
+    for (; cb + 1 < NCB; ++cb) {
+        VS_BLOCK(false)
+        const unsigned t = pc; pc = pn; pn = t;
+    }
+    VS_BLOCK(true)
+    if (wr == 0) VS_BAR()
+#undef VS_BLOCK
+#undef VS_TAP
+#undef VS_TAPWAIT
+#undef VS_WAIT
+#undef VS_COMPUTE
+#undef VS_BAR
+#undef VS_MM
+#undef VS_LGK0
+#undef VS_RD_B
+#undef VS_RD_A
+#undef VS_STAGE_B
+#undef VS_CVT_P
+#undef VS_STAGE_P
+    __syncthreads();  // every wave is done with the ring before an epilogue reuses it
+}
+
 // ---- 256 x 128 tile on the split main loop (the Cout = 128 convolutions of the pts3d head; round 3).  8 waves as 4 (M) x 2 (N), wave
 // tile 64 x 64 (acc[4][4]); a K-tile of 32 k is THREE 16 KiB units: A_h = tile rows {wm*64 + h*32 + 0..31 : wm = 0..3} (h = 0, 1) and B =
 // the 128 weight rows; ring of 2 slots x 3 units = 96 KiB.  Wave group g = wid >> 2 owns tile rows 128 g .. 128 g + 127, i.e. unit rows
