@@ -9,8 +9,9 @@ tests/test_gemm_routes_gpu.py.
   * `make_case`  -- one seeded input set in guarded buffers: lda, ldw > K with NaN padding columns, NaN in every A row outside the input
     row map, ldo > N and spare output rows pre-filled with a sentinel, optional odd strides and pointers offset by one element.  Every view
     lies inside one allocation, so nothing is ever out of bounds.
-  * `plan`       -- a line-by-line transcription of the dispatcher of csrc/gemm.hip (launch, launch_tail, launch_f32, launch_skinny,
-    launch_smallm): the kernels a call reaches, e.g. "g256(rows=16384)+tail:mi4(ks=2)".  It moves together with gemm.hip.
+  * `plan`       -- a line-by-line transcription of the dispatcher, csrc/routes.h (gemm_plan, tail_step, skinny_step, smallm_step): the
+    kernels a call reaches, e.g. "g256(rows=16384)+tail:mi4(ks=2)".  tests/test_routes_cpu.py compiles routes.h for the host and compares
+    the two string for string; the GPU tests name their routes from this copy, since there may be no compiler where they run.
   * `CASES`      -- the table of tests/test_gemm_routes_gpu.py; the first part of every id is the route written down by hand, which
     tests/test_gemm_ref_cpu.py compares with plan().
 
@@ -42,83 +43,82 @@ def cdiv(a, b):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
-# route plan: csrc/gemm.hip, line numbers of the statement transcribed
+# route plan: csrc/routes.h, the function transcribed (VS_DETERMINISTIC unset)
 # ------------------------------------------------------------------------------------------------------------------------------------
-def _smallm(rows, K2):                                            # launch_smallm, gemm.hip:469-474
-    one, deep = rows <= 16, K2 // 32 >= 64                        # :471
-    return "smallm<NW%d,MF%d>" % (16 if deep else 8, 1 if one else 4)   # :472-473
+def _smallm(rows, K2):                                            # smallm_step
+    one, deep = rows <= 16, K2 // 32 >= 64
+    return "smallm<NW%d,MF%d>" % (16 if deep else 8, 1 if one else 4)
 
 
-def _skinny(rows, N, K2, epi, resid):                             # launch_skinny, gemm.hip:435-441
-    gy, gx = cdiv(rows, 64), cdiv(N, 64)                          # :436
-    ks = 1                                                        # :438
-    if epi == 2 and not resid:                                    # :439 (VS_DETERMINISTIC unset)
-        while ks < 8 and gx * gy * ks * 2 <= 384 and K2 // 64 // (ks * 2) >= 32:   # :440
+def _skinny(rows, N, K2, epi, resid):                             # skinny_step
+    gy, gx = cdiv(rows, 64), cdiv(N, 64)
+    ks = 1
+    if epi == 2 and not resid:
+        while ks < 8 and gx * gy * ks * 2 <= 384 and K2 // 64 // (ks * 2) >= 32:
             ks *= 2
     return "skinny(ks=%d)" % ks
 
 
-def _tail(sp, rem, N, K2, epi, resid, ap, op):                    # launch_tail, gemm.hip:663-691
+def _tail(sp, rem, N, K2, epi, resid, ap, op):                    # tail_step
     ks = 1
-    if epi == 2 and rem > 64 and not resid:                       # :668
-        tiles = cdiv(rem, 128) * cdiv(N, 128)                     # :669
-        while ks < 8 and (K2 // 32) % (ks * 2) == 0 and K2 // 32 // (ks * 2) >= 8 and tiles * ks * 2 <= 512:   # :671
+    if epi == 2 and rem > 64 and not resid:
+        tiles = cdiv(rem, 128) * cdiv(N, 128)
+        while ks < 8 and (K2 // 32) % (ks * 2) == 0 and K2 // 32 // (ks * 2) >= 8 and tiles * ks * 2 <= 512:
             ks *= 2
-    # :679 holds for the three classes that reach launch_tail (the f32 class has no tail)
-    if rem <= 256 and K2 % 64 == 0 and (rem > 64 or epi in (4, 5) or op) and (sp or (not ap and not op)):     # :681
-        return "tail:" + _skinny(rem, N, K2, epi, resid)          # :683
-    if rem <= 64 and epi not in (4, 5) and not op and (sp or not ap):   # :686
-        return "tail:" + _smallm(rem, K2)                         # :688
-    return "tail:mi4(ks=%d)" % ks                                 # :690
+    if rem <= 256 and K2 % 64 == 0 and (rem > 64 or epi in (4, 5) or op) and (sp or (not ap and not op)):     # skinny_takes and ...
+        return "tail:" + _skinny(rem, N, K2, epi, resid)
+    if rem <= 64 and epi not in (4, 5) and not op and (sp or not ap):   # smallm_takes
+        return "tail:" + _smallm(rem, K2)
+    return "tail:mi4(ks=%d)" % ks
 
 
 def plan_info(cls, M, N, K, epi, resid=False, a_packed=False, out_packed=False):
     """-> (plan string, rows of the main launch).  K as given to the ABI; it doubles for the f32 and split classes (gemm_entry,
-    gemm.hip:893: f32 rows are addressed in 2-byte units)."""
+    gemm.hip: f32 rows are addressed in 2-byte units)."""
     assert cls in CLASSES
     K2 = 2 * K if cls in ("f32x", "split") else K
     ap, op = a_packed, out_packed
-    if cls == "f32x":                                             # launch_f32, gemm.hip:696-700
-        if M <= 64 and epi != 4:                                  # :697
+    if cls == "f32x":                                             # gemm_plan, the f32 class: no tail
+        if M <= 64 and epi != 4:
             return _smallm(M, K2), M
-        return ("g256(rows=%d)" % M if K2 % 128 == 0 else "mi4(rows=%d)" % M), M   # :698-699
+        return ("g256(rows=%d)" % M if K2 % 128 == 0 else "mi4(rows=%d)" % M), M
     sp = cls == "split"
-    if M <= 64 and epi not in (4, 5) and not op and (sp or not ap):   # launch, gemm.hip:705
+    if M <= 64 and epi not in (4, 5) and not op and (sp or not ap):   # gemm_plan: smallm_takes
         return _smallm(M, K2), M
-    if M <= 256 and K2 % 64 == 0 and (sp or (not ap and not op)):     # :707-709 (no taps, partials, K slices or window extras from these entries)
+    if M <= 256 and K2 % 64 == 0 and (sp or (not ap and not op)):     # skinny_takes
         return _skinny(M, N, K2, epi, resid), M
-    if K2 % 128 == 0 and M >= 256:                                # :715
-        tn, mt = cdiv(N, 256), M // 256                           # :716
-        full, rounds_all = mt * tn, (cdiv(M, 256) * tn + 255) // 256   # :717
-        mt_main = mt                                              # :718
-        if full > 256 and full % 256 != 0:                        # :719
+    if K2 % 128 == 0 and M >= 256:                                # whole rounds of 256 x 256 tiles + a tail
+        tn, mt = cdiv(N, 256), M // 256
+        full, rounds_all = mt * tn, (cdiv(M, 256) * tn + 255) // 256
+        mt_main = mt
+        if full > 256 and full % 256 != 0:
             mt_main = (full // 256) * 256 // tn
-        rows_main = mt_main * 256                                 # :720
+        rows_main = mt_main * 256
         rem = M - rows_main
-        tiles4 = cdiv(rem, 128) * cdiv(N, 128)                    # :722
-        cost_split = float((mt_main * tn + 255) // 256) + (0.31 * float((tiles4 + 767) // 768) if rem > 0 else 0.0)   # :723
-        tiles_one = cdiv(M, 256) * tn                             # :724
-        nearly_full = tiles_one * 100 >= rounds_all * 256 * 95    # :727
-        split = (not nearly_full) and rem > 0 and mt_main > 0 and cost_split < float(rounds_all) - 0.05   # :728
-        if split or tiles_one * 100 >= rounds_all * 256 * 70:     # :731
-            if not split:                                         # :735
+        tiles4 = cdiv(rem, 128) * cdiv(N, 128)
+        cost_split = float((mt_main * tn + 255) // 256) + (0.31 * float((tiles4 + 767) // 768) if rem > 0 else 0.0)
+        tiles_one = cdiv(M, 256) * tn
+        nearly_full = tiles_one * 100 >= rounds_all * 256 * 95
+        split = (not nearly_full) and rem > 0 and mt_main > 0 and cost_split < float(rounds_all) - 0.05
+        if split or tiles_one * 100 >= rounds_all * 256 * 70:
+            if not split:
                 return "g256(rows=%d)" % M, M
-            return "g256(rows=%d)+%s" % (rows_main, _tail(sp, rem, N, K2, epi, resid, ap, op)), rows_main   # :736
-    tiles_n = cdiv(N, 128)                                        # :741
-    t8 = cdiv(M, 256) * tiles_n                                   # :742
-    mi = 8 if t8 >= 256 else 4                                    # :743
+            return "g256(rows=%d)+%s" % (rows_main, _tail(sp, rem, N, K2, epi, resid, ap, op)), rows_main
+    tiles_n = cdiv(N, 128)                                        # 256 x 128 or 128 x 128 tiles, a tail of <= half a tile peeled
+    t8 = cdiv(M, 256) * tiles_n
+    mi = 8 if t8 >= 256 else 4
     bm, slots = 32 * mi, 256 * (2 if mi == 8 else 3)
-    rem = M % bm                                                  # :744
-    full = (M // bm) * tiles_n                                    # :745
+    rem = M % bm
+    full = (M // bm) * tiles_n
     split = full > 0 and 0 < rem <= bm // 2 and ((full + tiles_n + slots - 1) // slots > (full + slots - 1) // slots or
-                                                 (full + tiles_n + 255) // 256 > (full + 255) // 256)   # :749-750
-    m_main = M - rem if split else M                              # :752
+                                                 (full + tiles_n + 255) // 256 > (full + 255) // 256)
+    m_main = M - rem if split else M
     tail = "+" + _tail(sp, rem, N, K2, epi, resid, ap, op) if split else ""
-    if sp:                                                        # :756
-        tiles4 = cdiv(m_main, 128) * tiles_n                      # :757
-        if mi == 4 and epi == 2 and tiles4 <= 192 and m_main > 64:   # :758
-            return "mi2(rows=%d)%s" % (m_main, tail), m_main      # :760-762
-    return "mi%d(rows=%d)%s" % (mi, m_main, tail), m_main         # :768-770
+    if sp:                                                        # 64-row tiles for small residual-epilogue GEMMs
+        tiles4 = cdiv(m_main, 128) * tiles_n
+        if mi == 4 and epi == 2 and tiles4 <= 192 and m_main > 64:
+            return "mi2(rows=%d)%s" % (m_main, tail), m_main
+    return "mi%d(rows=%d)%s" % (mi, m_main, tail), m_main
 
 
 def plan(cls, M, N, K, epi, resid=False, a_packed=False, out_packed=False) -> str:

@@ -86,6 +86,21 @@ def test_pts3d_route_runs_its_sequence(calls, cls, BT, gh, gw, route, trunk_pack
     assert bool(torch.isfinite(out).all())
 
 
+def test_packed_trunk_map_gives_the_plain_map_s_bits_in_a_ragged_last_tile():
+    """BT = 47 frames of 19 x 1 tokens: head[0] sees 57 152 pixels = 223.25 tiles of 256, the smallest count that conv3x3_route (csrc/routes.h)
+    sends to the 256 x 128 tile kernel, so pts3d_route packs the trunk map there; the packed and the plain input must give the same bits."""
+    assert dpt.pts3d_route("split", 47, 19, 1, 256, 128, 128) == ("split_packed_dot", True)
+    assert dpt.pts3d_route("split", 46, 19, 1, 256, 128, 128) == ("split_packed_dot", False)
+    g = torch.Generator().manual_seed(1)
+    x = torch.randn(47, 76, 4, 256, generator=g).cuda()
+    w = ops.pack_conv3x3_weight((torch.randn(128, 256, 3, 3, generator=g) / 48).cuda(), "split")
+    b = torch.randn(128, generator=g).cuda()
+    plain = ops.conv3x3_nhwc(ops.upsample2x_nhwc(x), w, b)
+    packed = ops.conv3x3_nhwc(ops.upsample2x_nhwc(x, packed=True), w, b)
+    assert plain.shape[0] * plain.shape[1] * plain.shape[2] == 57152
+    assert torch.equal(plain.view(torch.int32), packed.view(torch.int32))
+
+
 @pytest.mark.parametrize("cls,gh,gw,route,stem,forced", [
     ("split", 2, 2, "split_stream_stem", "stream", False),
     ("split", 3, 3, "split_stem_up", "split7", False),

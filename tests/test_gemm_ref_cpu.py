@@ -232,7 +232,7 @@ def test_every_leaf_of_a_class_is_the_plan_of_a_case(cls):
 
 
 def test_plan_examples_from_the_dispatcher_comments():
-    """Shapes whose route the comments of csrc/gemm.hip spell out."""
+    """Shapes whose route the comments of csrc/routes.h spell out."""
     assert plan("f16", 2056, 4096, 1024, 0) == "mi8(rows=2048)+tail:smallm<NW8,MF1>"         # "peeling the 8 leftover rows makes it one"
     assert plan("split", 2056, 1024, 1024, 2) == "mi2(rows=2056)"                            # "64-row tiles ... double the workgroups"
     assert plan("f16", 16684, 1024, 512, 2) == "g256(rows=16384)+tail:mi4(ks=2)"

@@ -9,7 +9,10 @@
 // per-row source pointer changes with the tap, and out-of-image taps read a 128-byte zero page.  No im2col buffer ever
 // exists.  Fused: ReLU on the input (ResidualConvUnit applies the activation BEFORE each conv), bias, residual add,
 // ReLU on the output.
+#include <type_traits>
+
 #include "gemm256.h"
+#include "routes.h"
 
 __device__ __attribute__((aligned(128))) unsigned short vs_zero_page[64] = {0};
 
@@ -1114,6 +1117,21 @@ upsample2x_backward_kernel(const unsigned short *__restrict__ dout, unsigned sho
 
 }  // namespace
 
+template <int V> using ic = std::integral_constant<int, V>;
+
+// launch(ic<NF>) for NF = C2pad / 16 in 1 .. 6: the fused conv3x3 -> 1x1 kernels carry the width of the second layer as a template argument
+template <class F>
+static void with_head_nf(int C2pad, F &&launch) {
+    switch (C2pad / 16) {
+        case 1: launch(ic<1>{}); break;
+        case 2: launch(ic<2>{}); break;
+        case 3: launch(ic<3>{}); break;
+        case 4: launch(ic<4>{}); break;
+        case 5: launch(ic<5>{}); break;
+        default: launch(ic<6>{}); break;
+    }
+}
+
 static int conv3x3_entry(const void *in, const void *w, const float *bias, const void *residual, void *out, int32_t Nimg,
                          int32_t Hin, int32_t Win, int32_t Cin, int32_t Cout, int32_t stride, int32_t relu_in, int32_t relu_out,
                          int32_t dtype, float acc_scale, vs_stream_t stream_, const float *residual2 = nullptr) {
@@ -1131,83 +1149,46 @@ static int conv3x3_entry(const void *in, const void *w, const float *bias, const
     VS_CHECK(relu_out >= 0 && relu_out <= 2 && (relu_out != 2 || residual), "vs_conv3x3_nhwc: relu_out must be 0, 1 or 2 (2 = mask by `residual`, which must be given)");
     VS_CHECK(((uintptr_t)in & 15) == 0 && ((uintptr_t)w & 15) == 0, "vs_conv3x3_nhwc: 16-byte alignment required");
     if (Nimg == 0) return 0;
-    const int in_packed = (relu_in & 16) ? 1 : 0;      // + 16 (split class): `in` is the packed (hi, lo) image, its ReLU already applied by the producer
-    relu_in &= ~16;
+    const int in_packed = vs::route::take_packed_flag(relu_in);      // + 16 (split class): `in` is the packed (hi, lo) image, its ReLU already applied by the producer
     VS_CHECK(!in_packed || (dtype == 4 && relu_in == 0), "vs_conv3x3_split_nhwc: a packed input is a split-class operand that carries its ReLU already");
     ConvArgs g{(const unsigned short *)in, (const unsigned short *)w, bias, (const unsigned short *)residual, (unsigned short *)out,
                Nimg, H, W, Cin, Cout, relu_in, relu_out, Hin, Win, stride, nullptr, nullptr, nullptr, 0, 0, 0, acc_scale, 1.f, in_packed, residual2};
     VS_CHECK(!residual2 || ((dtype == 3 || dtype == 4) && relu_out != 2), "vs_conv3x3_nhwc: a second residual needs f32 activations (dtype 3 / 4) and no mask epilogue");
-    const long long M = (long long)Nimg * H * W;
-    int cshift = -1;
-    for (int sft = 0; sft < 4; ++sft)
-        if (Cin == (64 << sft)) cshift = sft;
-    // round 5: the 256 x 256 tile kernel takes any Cin that is a whole number of 64-unit K-tiles per tap (96 -> 128, 192, 384, 768 channels of
-    // the DPT reassemble / layer_rn convolutions and the stride-2 768 -> 768 convolution used to run on the 4-wave kernels at 170-270 TF/s)
-    const int kpt_any = (Cin % 64 == 0 && Cin / 64 <= 64) ? Cin / 64 : -1;
-    const long long t256 = vs::cdiv64(M, 256) * vs::cdiv(Cout, 256);
-    // >= 150 tiles (round 5; was 224): a 59 %-full round of 256 x 256 tiles beats the 4-wave kernel's one and a half rounds at two workgroups
-    // per CU in the split class (16 x 16 maps of the bench step: 0.21 -> 0.17 ms per convolution); 8 x 8 maps (48 tiles) stay where they were
-    const long long t256_min = dtype == 4 ? 150 : 224;
-    // the halo-tile body of the split-class 256-wide route (conv3x3_256_halo_split_kernel), for the shapes it covers; M / 256 tiles either way
-    const bool halo = dtype == 4 && stride == 1 && Cout == 256 && H % 16 == 0 && W % 16 == 0 && !g.a_packed && (long long)H * W * Cin < 2147483647LL;
-    if (dtype == 4 && cshift < 0 && kpt_any > 0 && Cout % 256 == 0 && (9 * kpt_any) % 2 == 0 && t256 >= t256_min && !g.a_packed) {
-        dim3 grid((unsigned)t256), block(512);
-        if (halo && relu_in) hipLaunchKernelGGL((conv3x3_256_halo_split_kernel<true>), grid, block, 0, stream, g, kpt_any);
-        else if (halo) hipLaunchKernelGGL((conv3x3_256_halo_split_kernel<false>), grid, block, 0, stream, g, kpt_any);
-        else if (relu_in) hipLaunchKernelGGL((conv3x3_256_kernel<kDtSplit, true>), grid, block, 0, stream, g, kpt_any);
-        else hipLaunchKernelGGL((conv3x3_256_kernel<kDtSplit, false>), grid, block, 0, stream, g, kpt_any);
-        VS_HIP(hipGetLastError());
-        return 0;
-    }
-    if (cshift >= 0 && Cout % 256 == 0 && (9 * Cin / 64) % 2 == 0 && t256 >= t256_min) {
-        dim3 grid((unsigned)t256), block(512);
-        if (dtype == 4) {
-            if (g.a_packed) hipLaunchKernelGGL((conv3x3_256_kernel<kDtSplit, false, 0, true>), grid, block, 0, stream, g, 1 << cshift);
-            else if (halo && relu_in) hipLaunchKernelGGL((conv3x3_256_halo_split_kernel<true>), grid, block, 0, stream, g, 1 << cshift);
-            else if (halo) hipLaunchKernelGGL((conv3x3_256_halo_split_kernel<false>), grid, block, 0, stream, g, 1 << cshift);
-            else if (relu_in) hipLaunchKernelGGL((conv3x3_256_kernel<kDtSplit, true>), grid, block, 0, stream, g, 1 << cshift);
-            else hipLaunchKernelGGL((conv3x3_256_kernel<kDtSplit, false>), grid, block, 0, stream, g, 1 << cshift);
-        } else if (dtype == 3) {
-            if (relu_in) hipLaunchKernelGGL((conv3x3_256_kernel<kDtF32, true>), grid, block, 0, stream, g, 1 << cshift);
-            else hipLaunchKernelGGL((conv3x3_256_kernel<kDtF32, false>), grid, block, 0, stream, g, 1 << cshift);
-        } else if (dtype == 2) {
-            if (relu_in) hipLaunchKernelGGL((conv3x3_256_kernel<true, true>), grid, block, 0, stream, g, 1 << cshift);
-            else hipLaunchKernelGGL((conv3x3_256_kernel<true, false>), grid, block, 0, stream, g, 1 << cshift);
-        } else {
-            if (relu_in) hipLaunchKernelGGL((conv3x3_256_kernel<false, true>), grid, block, 0, stream, g, 1 << cshift);
-            else hipLaunchKernelGGL((conv3x3_256_kernel<false, false>), grid, block, 0, stream, g, 1 << cshift);
-        }
-        VS_HIP(hipGetLastError());
-        return 0;
-    }
-    const long long big = vs::cdiv64(M, 256) * vs::cdiv(Cout, BN);
-    if (dtype == 4) {
-        VS_CHECK(Cin % 64 == 0, "vs_conv3x3_split_nhwc: Cin must be a multiple of 32");
-        if (cshift >= 0 && Cout % 128 == 0 && Cout % 256 != 0 && (9 * Cin / 64) % 2 == 0 && big >= 224) {   // `big >= 224` has a twin, PACKED_CONV_MIN_PIXELS in model/encoder/heads/dpt.py: change both.  (Cout = 256 maps too small for the 256 x 256 kernel: the 4-wave kernel is 8 % faster there, measured)
-            dim3 grid((unsigned)(vs::cdiv64(M, 256) * (Cout / 128))), block(512);
-            if (g.a_packed) hipLaunchKernelGGL((conv3x3_256x128_split_kernel<false, false, true>), grid, block, 0, stream, g, 1 << cshift);
-            else if (relu_in) hipLaunchKernelGGL((conv3x3_256x128_split_kernel<true, false>), grid, block, 0, stream, g, 1 << cshift);
-            else hipLaunchKernelGGL((conv3x3_256x128_split_kernel<false, false>), grid, block, 0, stream, g, 1 << cshift);
-            VS_HIP(hipGetLastError());
-            return 0;
-        }
-        VS_CHECK(!g.a_packed, "vs_conv3x3_split_nhwc: a packed input is taken by the 256 x 256 and 256 x 128 tile kernels only (this shape runs on the 4-wave kernel)");
-        // round 6, small batches (one 8-view scene: 16 x 16 / 32 x 32 maps = 2 048 / 8 192 pixels x 256 channels = 32 / 128 tiles of 128 x 128 for
-        // 256 CUs): 64-row tiles (MI = 2, the same kernel) double the workgroups.
-        const long long t4 = vs::cdiv64(M, 128) * vs::cdiv(Cout, BN);
-        if (big >= 512) hipLaunchKernelGGL((conv3x3_kernel<kDtSplit, 8>), dim3((unsigned)big), dim3(256), 0, stream, g);
-        else if (t4 <= 192 && M > 64) hipLaunchKernelGGL((conv3x3_kernel<kDtSplit, 2>), dim3((unsigned)(vs::cdiv64(M, 64) * vs::cdiv(Cout, BN))), dim3(256), 0, stream, g);
-        else hipLaunchKernelGGL((conv3x3_kernel<kDtSplit, 4>), dim3((unsigned)t4), dim3(256), 0, stream, g);
+    VS_CHECK(dtype != 4 || Cin % 64 == 0, "vs_conv3x3_split_nhwc: Cin must be a multiple of 32");
+    using vs::route::ConvKind;
+    const vs::route::ConvRoute r = vs::route::conv3x3_route(dtype, (long long)Nimg * H * W, H, W, Cin, Cout, stride, in_packed);      // routes.h
+    VS_CHECK(r.kind != ConvKind::PackedNotTaken, "vs_conv3x3_split_nhwc: a packed input is taken by the 256 x 256 and 256 x 128 tile kernels only (this shape runs on the 4-wave kernel)");
+    const dim3 grid((unsigned)r.grid), b512(512), b256(256);
+    if (r.kind == ConvKind::Halo256) {
+        if (relu_in) hipLaunchKernelGGL((conv3x3_256_halo_split_kernel<true>), grid, b512, 0, stream, g, r.kpt);
+        else hipLaunchKernelGGL((conv3x3_256_halo_split_kernel<false>), grid, b512, 0, stream, g, r.kpt);
+    } else if (r.kind == ConvKind::Tile256 && in_packed) {
+        hipLaunchKernelGGL((conv3x3_256_kernel<kDtSplit, false, 0, true>), grid, b512, 0, stream, g, r.kpt);
+    } else if (r.kind == ConvKind::Tile256) {
+        auto tile = [&](auto cls) {
+            if (relu_in) hipLaunchKernelGGL((conv3x3_256_kernel<decltype(cls)::value, true>), grid, b512, 0, stream, g, r.kpt);
+            else hipLaunchKernelGGL((conv3x3_256_kernel<decltype(cls)::value, false>), grid, b512, 0, stream, g, r.kpt);
+        };
+        if (dtype == 4) tile(ic<kDtSplit>{});
+        else if (dtype == 3) tile(ic<kDtF32>{});
+        else if (dtype == 2) tile(ic<1>{});
+        else tile(ic<0>{});
+    } else if (r.kind == ConvKind::Tile256x128) {
+        if (in_packed) hipLaunchKernelGGL((conv3x3_256x128_split_kernel<false, false, true>), grid, b512, 0, stream, g, r.kpt);
+        else if (relu_in) hipLaunchKernelGGL((conv3x3_256x128_split_kernel<true, false>), grid, b512, 0, stream, g, r.kpt);
+        else hipLaunchKernelGGL((conv3x3_256x128_split_kernel<false, false>), grid, b512, 0, stream, g, r.kpt);
+    } else if (dtype == 4) {      // the 4-wave kernel: each class has the tile heights (32 * MI rows) its route can return
+        if (r.mi == 8) hipLaunchKernelGGL((conv3x3_kernel<kDtSplit, 8>), grid, b256, 0, stream, g);
+        else if (r.mi == 2) hipLaunchKernelGGL((conv3x3_kernel<kDtSplit, 2>), grid, b256, 0, stream, g);
+        else hipLaunchKernelGGL((conv3x3_kernel<kDtSplit, 4>), grid, b256, 0, stream, g);
     } else if (dtype == 3) {
-        hipLaunchKernelGGL((conv3x3_kernel<kDtF32, 4>), dim3((unsigned)(vs::cdiv64(M, 128) * vs::cdiv(Cout, BN))), dim3(256), 0, stream, g);
-    } else if (big >= 256) {
-        dim3 grid((unsigned)big);
-        if (dtype == 2) hipLaunchKernelGGL((conv3x3_kernel<true, 8>), grid, dim3(256), 0, stream, g);
-        else hipLaunchKernelGGL((conv3x3_kernel<false, 8>), grid, dim3(256), 0, stream, g);
+        hipLaunchKernelGGL((conv3x3_kernel<kDtF32, 4>), grid, b256, 0, stream, g);
+    } else if (r.mi == 8) {
+        if (dtype == 2) hipLaunchKernelGGL((conv3x3_kernel<1, 8>), grid, b256, 0, stream, g);
+        else hipLaunchKernelGGL((conv3x3_kernel<0, 8>), grid, b256, 0, stream, g);
     } else {
-        dim3 grid((unsigned)(vs::cdiv64(M, 128) * vs::cdiv(Cout, BN)));
-        if (dtype == 2) hipLaunchKernelGGL((conv3x3_kernel<true, 4>), grid, dim3(256), 0, stream, g);
-        else hipLaunchKernelGGL((conv3x3_kernel<false, 4>), grid, dim3(256), 0, stream, g);
+        if (dtype == 2) hipLaunchKernelGGL((conv3x3_kernel<1, 4>), grid, b256, 0, stream, g);
+        else hipLaunchKernelGGL((conv3x3_kernel<0, 4>), grid, b256, 0, stream, g);
     }
     VS_HIP(hipGetLastError());
     return 0;
@@ -1257,25 +1238,15 @@ extern "C" int vs_conv3x3_head1x1_nhwc(const void *in, const void *w, const floa
     ConvArgs g{(const unsigned short *)in, (const unsigned short *)w, bias, nullptr, nullptr, Nimg, H, W, Cin, Cout, relu_in, relu_out, H, W, 1,
                (const unsigned short *)w2, bias2, (unsigned short *)out2, C2, C2pad, ld2, 1.f, 1.f};
     if (Cout == 256) {
-        int cshift = -1;
-        for (int sft = 0; sft < 4; ++sft)
-            if (Cin == (64 << sft)) cshift = sft;
+        const int cshift = vs::route::conv_cshift(Cin);
         VS_CHECK(cshift >= 0 && (9 * Cin / 64) % 2 == 0, "vs_conv3x3_head1x1_nhwc: Cin=%d not supported with Cout=256", Cin);
         VS_CHECK(C2pad % 16 == 0 && C2pad >= 16 && C2pad <= 96 && C2 <= C2pad && ld2 >= C2pad && ld2 % 4 == 0 && !relu_in,
                  "vs_conv3x3_head1x1_nhwc: need C2pad in 16..96 (multiple of 16), ld2 >= C2pad, no relu_in (C2pad=%d ld2=%d)", C2pad, ld2);
         dim3 grid((unsigned)(M / 256)), block(512);
-#define VS_FUSE(NF_)                                                                                                        \
-        if (dtype == 2) hipLaunchKernelGGL((conv3x3_256_kernel<1, false, NF_>), grid, block, 0, stream, g, 1 << cshift);         \
-        else hipLaunchKernelGGL((conv3x3_256_kernel<0, false, NF_>), grid, block, 0, stream, g, 1 << cshift);
-        switch (C2pad / 16) {
-            case 1: VS_FUSE(1) break;
-            case 2: VS_FUSE(2) break;
-            case 3: VS_FUSE(3) break;
-            case 4: VS_FUSE(4) break;
-            case 5: VS_FUSE(5) break;
-            default: VS_FUSE(6) break;
-        }
-#undef VS_FUSE
+        with_head_nf(C2pad, [&](auto nf) {
+            if (dtype == 2) hipLaunchKernelGGL((conv3x3_256_kernel<1, false, decltype(nf)::value>), grid, block, 0, stream, g, 1 << cshift);
+            else hipLaunchKernelGGL((conv3x3_256_kernel<0, false, decltype(nf)::value>), grid, block, 0, stream, g, 1 << cshift);
+        });
     } else {
         VS_CHECK(Cout == 128 && C2 >= 1 && C2 <= 4 && ld2 >= 4 && ld2 % 4 == 0 && Cin % 32 == 0,
                  "vs_conv3x3_head1x1_nhwc: the dot-product form needs Cout = 128, C2 <= 4, ld2 >= 4 (Cout=%d C2=%d)", Cout, C2);
@@ -1294,8 +1265,7 @@ extern "C" int vs_conv3x3_head_dot_split_nhwc(const float *in, const void *wp, f
                                               float *out2, int32_t Nimg, int32_t H, int32_t W, int32_t Cin, int32_t C2, int32_t ld2, int32_t relu_in,
                                               int32_t relu_out, vs_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    const int in_packed = (relu_out & 16) ? 1 : 0;     // + 16: `in` is the packed (hi, lo) image of the f32 tensor (vs_upsample2x_nhwc ... + 16), ABI 5
-    relu_out &= ~16;
+    const int in_packed = vs::route::take_packed_flag(relu_out);     // + 16: `in` is the packed (hi, lo) image of the f32 tensor (vs_upsample2x_nhwc ... + 16), ABI 5
     VS_CHECK(in && wp && w2 && bias2 && out2 && acc_scale > 0.f, "vs_conv3x3_head_dot_split_nhwc: null pointer / bad scale");
     const long long M = (long long)Nimg * H * W;
     VS_CHECK(Nimg > 0 && H > 0 && W > 0 && H < 32767 && W < 65536 && M % 256 == 0 && M < 2147483647LL, "vs_conv3x3_head_dot_split_nhwc: N*H*W must be a positive multiple of 256");
@@ -1303,9 +1273,7 @@ extern "C" int vs_conv3x3_head_dot_split_nhwc(const float *in, const void *wp, f
     VS_CHECK((((uintptr_t)in | (uintptr_t)wp | (uintptr_t)out2 | (uintptr_t)bias2) & 15) == 0, "vs_conv3x3_head_dot_split_nhwc: 16-byte alignment required");
     ConvArgs g{(const unsigned short *)in, (const unsigned short *)wp, bias, nullptr, nullptr, Nimg, H, W, 2 * Cin, 128, relu_in, relu_out, H, W, 1,
                (const unsigned short *)w2, bias2, (unsigned short *)out2, C2, C2, ld2, acc_scale, 1.f};
-    int cshift = -1;
-    for (int sft = 0; sft < 4; ++sft)
-        if (2 * Cin == (64 << sft)) cshift = sft;
+    const int cshift = vs::route::conv_cshift(2 * Cin);
     const bool tile128 = cshift >= 0 && (9 * 2 * Cin / 64) % 2 == 0 && !relu_in;
     VS_CHECK(!in_packed || tile128, "vs_conv3x3_head_dot_split_nhwc: a packed input needs the 256 x 128 tile kernel (Cin in {32, 64, 128, 256}, no relu_in)");
     if (tile128 && in_packed)
@@ -1325,14 +1293,11 @@ extern "C" int vs_conv3x3_head1x1_split_nhwc(const float *in, const void *wp, fl
                                              const float *bias2, float *out2, int32_t Nimg, int32_t H, int32_t W, int32_t Cin, int32_t C2, int32_t C2pad,
                                              int32_t ld2, int32_t relu_out, vs_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    const int in_packed = (relu_out & 16) ? 1 : 0;     // + 16: `in` is the packed (hi, lo) image of the f32 tensor (vs_upsample2x_nhwc relu_add + 16, ...)
-    relu_out &= ~16;
+    const int in_packed = vs::route::take_packed_flag(relu_out);     // + 16: `in` is the packed (hi, lo) image of the f32 tensor (vs_upsample2x_nhwc relu_add + 16, ...)
     VS_CHECK(in && wp && w2p && bias2 && out2 && acc_scale > 0.f && acc_scale2 > 0.f, "vs_conv3x3_head1x1_split_nhwc: null pointer / bad scale");
     const long long M = (long long)Nimg * H * W;
     VS_CHECK(Nimg > 0 && H > 0 && W > 0 && H < 32767 && W < 65536 && M % 256 == 0 && M < 2147483647LL, "vs_conv3x3_head1x1_split_nhwc: N*H*W must be a positive multiple of 256");
-    int cshift = -1;
-    for (int sft = 0; sft < 4; ++sft)
-        if (2 * Cin == (64 << sft)) cshift = sft;
+    const int cshift = vs::route::conv_cshift(2 * Cin);
     VS_CHECK(cshift >= 0 && (9 * 2 * Cin / 64) % 2 == 0, "vs_conv3x3_head1x1_split_nhwc: Cin=%d not supported", Cin);
     VS_CHECK(C2pad % 16 == 0 && C2pad >= 16 && C2pad <= 96 && C2 <= C2pad && ld2 >= C2pad && ld2 % 4 == 0 && (relu_out == 0 || relu_out == 1),
              "vs_conv3x3_head1x1_split_nhwc: need C2pad in 16..96 (multiple of 16), ld2 >= C2pad (C2pad=%d ld2=%d)", C2pad, ld2);
@@ -1342,17 +1307,10 @@ extern "C" int vs_conv3x3_head1x1_split_nhwc(const float *in, const void *wp, fl
                (const unsigned short *)w2p, bias2, (unsigned short *)out2, C2, C2pad, ld2, acc_scale, acc_scale2};
     dim3 grid((unsigned)(M / 256)), block(512);
     g.a_packed = in_packed;
-#define VS_HEAD(NF_) { if (in_packed) hipLaunchKernelGGL((conv3x3_256_kernel<kDtSplit, false, NF_, true>), grid, block, 0, stream, g, 1 << cshift); \
-                       else hipLaunchKernelGGL((conv3x3_256_kernel<kDtSplit, false, NF_>), grid, block, 0, stream, g, 1 << cshift); }
-    switch (C2pad / 16) {
-        case 1: VS_HEAD(1) break;
-        case 2: VS_HEAD(2) break;
-        case 3: VS_HEAD(3) break;
-        case 4: VS_HEAD(4) break;
-        case 5: VS_HEAD(5) break;
-        default: VS_HEAD(6) break;
-    }
-#undef VS_HEAD
+    with_head_nf(C2pad, [&](auto nf) {
+        if (in_packed) hipLaunchKernelGGL((conv3x3_256_kernel<kDtSplit, false, decltype(nf)::value, true>), grid, block, 0, stream, g, 1 << cshift);
+        else hipLaunchKernelGGL((conv3x3_256_kernel<kDtSplit, false, decltype(nf)::value>), grid, block, 0, stream, g, 1 << cshift);
+    });
     VS_HIP(hipGetLastError());
     return 0;
 }

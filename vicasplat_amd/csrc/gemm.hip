@@ -20,7 +20,10 @@
 //   3 STORE32   out32[row(m), n] = acc + bias
 // row(m) = (m / grp_in) * grp_out + grp_off + m % grp_in lets a GEMM write straight into a larger token buffer
 // (e.g. the 257 image tokens of a frame behind the frame's camera token).
+#include <type_traits>
+
 #include "gemm256.h"
+#include "routes.h"
 
 namespace {
 
@@ -431,46 +434,32 @@ __global__ void __launch_bounds__(512) gemm_skinny_kernel(const GemmArgs g_in) {
     gemm_epilogue<BF16, EPI, 1>(g, sum, wid < 4 ? m0 + wid * 16 : g.M, n0, rope_tab, wid, lane);
 }
 
+// Calls launch(std::integral_constant<int, E>) for E == epi in 0 .. MAXE; epilogue 5 (x GELU') exists in the split class only.
+template <int BF16, int MAXE, int E = 0, class F>
+int with_epilogue(int epi, F &&launch) {
+    if constexpr (E > MAXE) {
+        VS_CHECK(false, "vs_gemm_bias_act: unknown epilogue %d", epi);
+    } else if constexpr (E == 5 && BF16 != kDtSplit) {
+        VS_CHECK(epi != 5, "epilogue 5 (x GELU') is a split-class epilogue");
+        return with_epilogue<BF16, MAXE, E + 1>(epi, launch);
+    } else {
+        if (epi != E) return with_epilogue<BF16, MAXE, E + 1>(epi, launch);
+        launch(std::integral_constant<int, E>{});
+        return 0;
+    }
+}
+
+// (g.ksplit > 1: K split over blockIdx.z, route::skinny_step)
 template <int BF16>
 int launch_skinny(const GemmArgs &g, int epi, hipStream_t stream) {
-    const int rows = g.M - g.m_lo, gy = vs::cdiv(rows, 64), gx = vs::cdiv(g.N, 64);
-    // epilogue 2 with the residual already in `out`: split K over workgroups while the grid is small and a slice keeps >= 8 blocks per wave
-    int ks = 1;
-    if (epi == 2 && !g.resid && !vs::deterministic())
-        while (ks < 8 && gx * gy * ks * 2 <= 384 && g.K / 64 / (ks * 2) >= 32) ks *= 2;
-    dim3 grid(gx, gy, ks), block(512);
-    switch (epi) {
-        case 0: hipLaunchKernelGGL((gemm_skinny_kernel<BF16, 0>), grid, block, 0, stream, g); break;
-        case 1: hipLaunchKernelGGL((gemm_skinny_kernel<BF16, 1>), grid, block, 0, stream, g); break;
-        case 2: hipLaunchKernelGGL((gemm_skinny_kernel<BF16, 2>), grid, block, 0, stream, g); break;
-        case 3: hipLaunchKernelGGL((gemm_skinny_kernel<BF16, 3>), grid, block, 0, stream, g); break;
-        case 4: hipLaunchKernelGGL((gemm_skinny_kernel<BF16, 4>), grid, block, 0, stream, g); break;
-        case 5: if constexpr (BF16 == kDtSplit) { hipLaunchKernelGGL((gemm_skinny_kernel<BF16, 5>), grid, block, 0, stream, g); break; }
-                vs::set_error("epilogue 5 (x GELU') is a split-class epilogue"); return -1;
-        default: vs::set_error("vs_gemm_bias_act: unknown epilogue %d", epi); return -1;
-    }
-    return 0;
+    dim3 grid(vs::cdiv(g.N, 64), vs::cdiv(g.M - g.m_lo, 64), g.ksplit), block(512);
+    return with_epilogue<BF16, 5>(epi, [&](auto e) { hipLaunchKernelGGL((gemm_skinny_kernel<BF16, decltype(e)::value>), grid, block, 0, stream, g); });
 }
 
 template <int BF16, int NW, int MF>
-int launch_smallm_nw(const GemmArgs &g, int epi, hipStream_t stream) {
-    dim3 grid(vs::cdiv(g.N, 16), vs::cdiv(g.M - g.m_lo, 16 * MF)), block(64 * NW);
-    switch (epi) {
-        case 0: hipLaunchKernelGGL((gemm_smallm_kernel<BF16, 0, NW, MF>), grid, block, 0, stream, g); break;
-        case 1: hipLaunchKernelGGL((gemm_smallm_kernel<BF16, 1, NW, MF>), grid, block, 0, stream, g); break;
-        case 2: hipLaunchKernelGGL((gemm_smallm_kernel<BF16, 2, NW, MF>), grid, block, 0, stream, g); break;
-        case 3: hipLaunchKernelGGL((gemm_smallm_kernel<BF16, 3, NW, MF>), grid, block, 0, stream, g); break;
-        default: vs::set_error("vs_gemm_bias_act: unknown epilogue %d", epi); return -1;
-    }
-    return 0;
-}
-
-template <int BF16>
 int launch_smallm(const GemmArgs &g, int epi, hipStream_t stream) {
-    // 16 waves split K when it is long (each walks <= 8 k-steps of 4096), 8 otherwise; 1 or 4 row fragments
-    const bool one = g.M - g.m_lo <= 16, deep = g.K / 32 >= 64;
-    if (one) return deep ? launch_smallm_nw<BF16, 16, 1>(g, epi, stream) : launch_smallm_nw<BF16, 8, 1>(g, epi, stream);
-    return deep ? launch_smallm_nw<BF16, 16, 4>(g, epi, stream) : launch_smallm_nw<BF16, 8, 4>(g, epi, stream);
+    dim3 grid(vs::cdiv(g.N, 16), vs::cdiv(g.M - g.m_lo, 16 * MF)), block(64 * NW);
+    return with_epilogue<BF16, 3>(epi, [&](auto e) { hipLaunchKernelGGL((gemm_smallm_kernel<BF16, decltype(e)::value, NW, MF>), grid, block, 0, stream, g); });
 }
 
 template <int BF16, int MI>
@@ -478,17 +467,7 @@ int launch_mi(const GemmArgs &g, int epi, hipStream_t stream) {
     const int nwg = vs::cdiv(g.M - g.m_lo, 32 * MI) * vs::cdiv(g.N, BN);
     dim3 grid(nwg, epi == 2 && g.ksplit > 1 ? g.ksplit : 1), block(256);
     if (epi == 2 && g.ntaps > 0) grid = dim3((unsigned)nwg * g.ntaps * g.ksplit, 1);
-    switch (epi) {
-        case 0: hipLaunchKernelGGL((gemm_kernel<BF16, 0, MI>), grid, block, 0, stream, g); break;
-        case 1: hipLaunchKernelGGL((gemm_kernel<BF16, 1, MI>), grid, block, 0, stream, g); break;
-        case 2: hipLaunchKernelGGL((gemm_kernel<BF16, 2, MI>), grid, block, 0, stream, g); break;
-        case 3: hipLaunchKernelGGL((gemm_kernel<BF16, 3, MI>), grid, block, 0, stream, g); break;
-        case 4: hipLaunchKernelGGL((gemm_kernel<BF16, 4, MI>), grid, block, 0, stream, g); break;
-        case 5: if constexpr (BF16 == kDtSplit) { hipLaunchKernelGGL((gemm_kernel<BF16, 5, MI>), grid, block, 0, stream, g); break; }
-                vs::set_error("epilogue 5 (x GELU') is a split-class epilogue"); return -1;
-        default: vs::set_error("vs_gemm_bias_act: unknown epilogue %d", epi); return -1;
-    }
-    return 0;
+    return with_epilogue<BF16, 5>(epi, [&](auto e) { hipLaunchKernelGGL((gemm_kernel<BF16, decltype(e)::value, MI>), grid, block, 0, stream, g); });
 }
 
 // 7x7 RGB stem as a window GEMM on the 256x256 kernel's main loop: a K-tile (64) is TWO kernel rows of 32 halfs (21 used), i.e. the
@@ -633,141 +612,43 @@ int launch_256(const GemmArgs &g, int epi, hipStream_t stream) {
     const int nwg = vs::cdiv(g.M - g.m_lo, 256) * vs::cdiv(g.N, 256);
     dim3 grid(nwg), block(512);
     if constexpr (BF16 == kDtSplit) {
-        if (g.a_packed) {
-            switch (epi) {
-                case 0: hipLaunchKernelGGL((gemm256_kernel<BF16, 0, true>), grid, block, 0, stream, g); break;
-                case 1: hipLaunchKernelGGL((gemm256_kernel<BF16, 1, true>), grid, block, 0, stream, g); break;
-                case 2: hipLaunchKernelGGL((gemm256_kernel<BF16, 2, true>), grid, block, 0, stream, g); break;
-                case 3: hipLaunchKernelGGL((gemm256_kernel<BF16, 3, true>), grid, block, 0, stream, g); break;
-                case 4: hipLaunchKernelGGL((gemm256_kernel<BF16, 4, true>), grid, block, 0, stream, g); break;
-                default: vs::set_error("vs_gemm_bias_act: unknown epilogue %d", epi); return -1;
-            }
-            return 0;
-        }
+        if (g.a_packed)
+            return with_epilogue<BF16, 4>(epi, [&](auto e) { hipLaunchKernelGGL((gemm256_kernel<BF16, decltype(e)::value, true>), grid, block, 0, stream, g); });
     }
-    switch (epi) {
-        case 0: hipLaunchKernelGGL((gemm256_kernel<BF16, 0>), grid, block, 0, stream, g); break;
-        case 1: hipLaunchKernelGGL((gemm256_kernel<BF16, 1>), grid, block, 0, stream, g); break;
-        case 2: hipLaunchKernelGGL((gemm256_kernel<BF16, 2>), grid, block, 0, stream, g); break;
-        case 3: hipLaunchKernelGGL((gemm256_kernel<BF16, 3>), grid, block, 0, stream, g); break;
-        case 4: hipLaunchKernelGGL((gemm256_kernel<BF16, 4>), grid, block, 0, stream, g); break;
-        case 5: if constexpr (BF16 == kDtSplit) { hipLaunchKernelGGL((gemm256_kernel<BF16, 5>), grid, block, 0, stream, g); break; }
-                vs::set_error("epilogue 5 (x GELU') is a split-class epilogue"); return -1;
-        default: vs::set_error("vs_gemm_bias_act: unknown epilogue %d", epi); return -1;
-    }
-    return 0;
+    return with_epilogue<BF16, 5>(epi, [&](auto e) { hipLaunchKernelGGL((gemm256_kernel<BF16, decltype(e)::value>), grid, block, 0, stream, g); });
 }
 
-// Rows [g.M - rem, g.M) of a split GEMM: <= 64 rows on the weight-streaming kernel, <= 128 on one row of 128x128 tiles.
-template <int BF16>
-int launch_tail(const GemmArgs &g, int rem, int epi, hipStream_t stream) {
-    GemmArgs t = g;
-    t.m_lo = g.M - rem;
-    // a tail is a handful of tiles walking all of K serially: for the f32 residual epilogue split K over up to 8 workgroups
-    // per tile (>= 8 k-steps each) and let the partial sums meet through f32 atomics
-    if (epi == 2 && rem > 64 && !g.resid && !vs::deterministic()) {   // (split-K partial sums meet in out: it must already hold the residual)
-        const int tiles = vs::cdiv(rem, 128) * vs::cdiv(g.N, BN);
-        int ks = 1;
-        while (ks < 8 && (g.K / 32) % (ks * 2) == 0 && g.K / 32 / (ks * 2) >= 8 && tiles * ks * 2 <= 512) ks *= 2;
-        t.ksplit = ks;
-    }
-    // (the RoPE epilogue pairs columns 16 apart and a packed output is written in 32-column blocks: only the tile kernels hold those in one
-    // workgroup).  Round 4: the weight-streaming kernel takes row groups of 64 (blockIdx.y) and packed A rows, so sending the 192-row tails
-    // of the bench step to it (plain stores of whole-K sums instead of the K-split tiles' f32 atomics) was measured same-box:
-    // 246.6 / 248.3 vs 247.6 / 247.7 ms per step -- no gain (A is re-read by each of the N / 16 column workgroups); tails of <= 64 rows stay.
-    // Round 5: tails of 65 .. 256 rows of the split class run on the skinny kernel (every epilogue, packed A / packed output included)
-    if constexpr (BF16 == kDtSplit || BF16 == 0 || BF16 == 1) {   // (split class and, since late round 5, the 16-bit classes)
-        // (<= 64 rows stay on the weight-streaming kernel where it applies; the RoPE epilogue and packed outputs, which it does not have, come here)
-        if (rem <= 256 && g.K % 64 == 0 && (rem > 64 || epi == 4 || epi == 5 || g.out_packed) && (BF16 == kDtSplit || (!g.a_packed && !g.out_packed))) {
-            t.ksplit = 1;
-            return launch_skinny<BF16>(t, epi, stream);
-        }
-    }
-    if (rem <= 64 && epi != 4 && epi != 5 && !g.out_packed && (BF16 == kDtSplit || !g.a_packed)) {
-        t.ksplit = 1;
-        return launch_smallm<BF16>(t, epi, stream);
-    }
-    return launch_mi<BF16, 4>(t, epi, stream);
-}
-
-// reference-precision path (exact f32 MFMA at 1/16 of the 16-bit rate): the matrix pipe, not the tile schedule, sets the time, so
-// there is one route per shape class and no tail splitting: 256x256 tiles when K allows (K in 2-byte units: a multiple of
-// 128 = 64 floats), 128x128 tiles otherwise, the weight-streaming kernel for the camera-token GEMMs
-int launch_f32(const GemmArgs &g, int epi, hipStream_t stream) {
-    if (g.M <= 64 && epi != 4) return launch_smallm<kDtF32>(g, epi, stream);
-    if (g.K % 128 == 0) return launch_256<kDtF32>(g, epi, stream);
-    return launch_mi<kDtF32, 4>(g, epi, stream);
-}
-
-// (tests/gemm_f64.py, plan(), transcribes this dispatcher -- launch, launch_tail, launch_f32, launch_skinny, launch_smallm -- line by line: change them together)
+// The forward dispatcher: the steps of route::gemm_plan (routes.h; tests/test_routes_cpu.py compares it with the route strings of the GPU
+// tests), each on a copy of the arguments narrowed to the step's rows.  Split operands (kDtSplit) take the 16-bit classes' routing.
 template <int BF16>
 int launch(const GemmArgs &g, int epi, hipStream_t stream) {
-    if (g.M <= 64 && epi != 4 && epi != 5 && !g.out_packed && (BF16 == kDtSplit || !g.a_packed)) return launch_smallm<BF16>(g, epi, stream);
-    if constexpr (BF16 == kDtSplit || BF16 == 0 || BF16 == 1) {   // camera-token GEMMs and other launches of <= 256 rows: the skinny kernel (round 5)
-        if (g.M - g.m_lo <= 256 && g.K % 64 == 0 && g.ntaps == 0 && !g.partials && g.ksplit <= 1 && g.a_sup_extra == 0 && g.a_kstride == 32 &&
-            (BF16 == kDtSplit || (!g.a_packed && !g.out_packed)))
-            return launch_skinny<BF16>(g, epi, stream);
-    }
-    // 256x256 tiles run one 8-wave workgroup per CU, i.e. in rounds of 256 tiles, and a partly filled round costs as much
-    // as a full one (M = frames * 257 tokens never divides).  So the big tiles only get as many rows as fill whole rounds;
-    // the remaining rows are finished by a launch of small tiles (128x128, 3 workgroups per CU) or, for <= 64 rows, the
-    // weight-streaming kernel -- a short round instead of a mostly idle long one.
-    if (g.K % 128 == 0 && g.M >= 256) {
-        const int tn = vs::cdiv(g.N, 256), mt = g.M / 256;
-        const long long full = (long long)mt * tn, rounds_all = (vs::cdiv(g.M, 256) * (long long)tn + 255) / 256;
-        int mt_main = mt;
-        if (full > 256 && full % 256 != 0) mt_main = (int)((full / 256) * 256 / tn);  // whole rounds only
-        const int rows_main = mt_main * 256, rem = g.M - rows_main;
-        // cost in units of one 256x256 round; a 128x128 round (768 tiles) is about 0.31 of it
-        const long long tiles4 = (long long)vs::cdiv(rem, 128) * vs::cdiv(g.N, 128);
-        const double cost_split = (double)(((long long)mt_main * tn + 255) / 256) + (rem > 0 ? 0.31 * (double)((tiles4 + 767) / 768) : 0.0);
-        const long long tiles_one = vs::cdiv(g.M, 256) * (long long)tn;
-        // a last round that is >= 95 % full is not worth a second launch (e.g. 31 eight-view scenes: 249 row tiles -> 3.89 / 11.67 /
-        // 15.56 rounds): one launch, no tail
-        const bool nearly_full = tiles_one * 100 >= rounds_all * 256 * 95;
-        const bool split = !nearly_full && rem > 0 && mt_main > 0 && cost_split < (double)rounds_all - 0.05;
-        // (a round that is >= 70 % full still beats the 256x128 tiles: 8 scenes x 257 tokens x 768 columns = 195 tiles, 385 vs 391 ms per
-        // split-class training step)
-        if (split || tiles_one * 100 >= rounds_all * 256 * 70) {
-            GemmArgs main_g = g;
-            if (split) main_g.M = rows_main;
-            int rc = launch_256<BF16>(main_g, epi, stream);
-            if (rc || !split) return rc;
-            return launch_tail<BF16>(g, rem, epi, stream);
+    using vs::route::Leaf;
+    static_assert(vs::route::kF32 == kDtF32 && vs::route::kSplit == kDtSplit && BN == 128, "routes.h restates these");
+    const vs::route::GemmPlan plan = vs::route::gemm_plan(BF16, g.M, g.N, g.K, epi, g.resid != nullptr, g.a_packed, g.out_packed, vs::deterministic());
+    for (int i = 0; i < plan.n; ++i) {
+        const vs::route::GemmStep &s = plan.step[i];
+        GemmArgs t = g;
+        t.M = s.m_hi; t.m_lo = s.m_lo; t.ksplit = s.ksplit;
+        int rc = -1;
+        if (s.leaf == Leaf::SmallM) {
+            rc = s.mf == 1 ? (s.nw == 16 ? launch_smallm<BF16, 16, 1>(t, epi, stream) : launch_smallm<BF16, 8, 1>(t, epi, stream))
+                           : (s.nw == 16 ? launch_smallm<BF16, 16, 4>(t, epi, stream) : launch_smallm<BF16, 8, 4>(t, epi, stream));
+        } else if (s.leaf == Leaf::G256) {
+            rc = launch_256<BF16>(t, epi, stream);
+        } else if (s.leaf == Leaf::Mi4) {
+            rc = launch_mi<BF16, 4>(t, epi, stream);
+        } else if constexpr (BF16 != kDtF32) {       // (the f32 class has these three leaves only)
+            if (s.leaf == Leaf::Skinny) rc = launch_skinny<BF16>(t, epi, stream);
+            else if (s.leaf == Leaf::Mi8) rc = launch_mi<BF16, 8>(t, epi, stream);
+            else if constexpr (BF16 == kDtSplit) {   // Leaf::Mi2: epilogue 2 only
+                const int nwg = vs::cdiv(s.m_hi - s.m_lo, 64) * vs::cdiv(g.N, BN);
+                hipLaunchKernelGGL((gemm_kernel<kDtSplit, 2, 2>), dim3((unsigned)nwg, 1), dim3(256), 0, stream, t);
+                rc = 0;
+            }
         }
+        if (rc) return rc;
     }
-    // 256x128 tiles (half the W-panel traffic and LDS-DMA issue per flop of 128x128) whenever there are enough of them
-    // to fill 256 CUs x 2 resident workgroups; 128x128 otherwise.
-    const int tiles_n = vs::cdiv(g.N, BN);
-    const long long t8 = (long long)vs::cdiv(g.M, 256) * tiles_n;
-    const int mi = t8 >= 256 ? 8 : 4, bm = 32 * mi, slots = 256 * (mi == 8 ? 2 : 3);
-    const int rem = g.M % bm;
-    const long long full = (long long)(g.M / bm) * tiles_n;
-    // a partly filled extra round costs a whole one.  Round 6: the matrix pipes of a CU are shared by its resident workgroups, so a "round"
-    // of MFMA-bound tiles is 256 tiles (one per CU), not `slots` -- one 8-view scene's fc1 (2 056 rows x 4 096 columns) is 288 tiles of
-    // 256 x 128, i.e. TWO rounds with the second 12 % full; peeling the 8 leftover rows makes it one (110 -> 70 us).
-    const bool split = full > 0 && rem > 0 && rem <= bm / 2 &&
-                       ((full + tiles_n + slots - 1) / slots > (full + slots - 1) / slots || (full + tiles_n + 255) / 256 > (full + 255) / 256);
-    GemmArgs main_g = g;
-    if (split) main_g.M = g.M - rem;
-    // Round 6, small batches (one 8-view scene = 2 056 rows): the residual epilogue's GEMMs (attention projection, fc2: N = 1024 / 768) are
-    // 136 / 102 tiles of 128 x 128 -- half the chip for one pass over K.  64-row tiles (MI = 2: the same kernel, each wave a 32 x 64 slab)
-    // double the workgroups.
-    if constexpr (BF16 == kDtSplit) {
-        const long long tiles4 = (long long)vs::cdiv(main_g.M - main_g.m_lo, 128) * tiles_n;
-        if (mi == 4 && epi == 2 && g.ntaps == 0 && g.ksplit <= 1 && !g.partials && tiles4 <= 192 && main_g.M - main_g.m_lo > 64) {
-            const long long nwg = (long long)vs::cdiv(main_g.M - main_g.m_lo, 64) * tiles_n;
-            hipLaunchKernelGGL((gemm_kernel<kDtSplit, 2, 2>), dim3((unsigned)nwg, 1), dim3(256), 0, stream, main_g);
-            if (!split) return 0;
-            return launch_tail<BF16>(g, rem, epi, stream);
-        }
-    }
-    // (Round 6, measured and not kept: cutting K over blockIdx.y for the 136-tile residual-epilogue GEMMs of a ONE-scene batch -- 2 056 rows,
-    // N = 1024: half the chip for one pass over K -- until the grid fills the chip.  The partial sums meet through f32 atomics and the
-    // epilogue's atomic traffic costs more than the idle CUs: B = 1 encoder 22.2 -> 26.2 ms, B = 2 29.7 -> 35.3 ms.)
-    int rc = mi == 8 ? launch_mi<BF16, 8>(main_g, epi, stream) : launch_mi<BF16, 4>(main_g, epi, stream);
-    if (rc || !split) return rc;
-    return launch_tail<BF16>(g, rem, epi, stream);
+    return 0;
 }
 
 // out[t][m, n] += sum_s partials[((s * ntaps + t) * M + m) * N + n]: second stage of a weight-gradient GEMM with a workspace.
@@ -926,10 +807,9 @@ int gemm_entry(const char *fn, const void *A, const void *W, const float *bias, 
     g.acc_scale = acc_scale;
     g.a_packed = a_packed;
     g.out_packed = out_packed;
-    // split operands (kDtSplit) take the 16-bit classes' routing: whole rounds of 256 x 256 tiles + a tail launch (K counts 2-byte units
-    // of the f32 rows; every stage pair / K-tile of the kernels is one 128-byte block of 32 k)
+    // (K counts 2-byte units of the f32 rows; every stage pair / K-tile of the kernels is one 128-byte block of 32 k)
     const int rc = dtype == 4 ? launch<kDtSplit>(g, epilogue, stream)
-                 : dtype == 3 ? launch_f32(g, epilogue, stream) : dtype == 2 ? launch<1>(g, epilogue, stream) : launch<0>(g, epilogue, stream);
+                 : dtype == 3 ? launch<kDtF32>(g, epilogue, stream) : dtype == 2 ? launch<1>(g, epilogue, stream) : launch<0>(g, epilogue, stream);
     if (rc) return rc;
     VS_HIP(hipGetLastError());
     return 0;

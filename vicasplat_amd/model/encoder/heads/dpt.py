@@ -22,9 +22,9 @@ from torch import nn
 
 from .... import ops
 
-# Twin of `big >= 224` in conv3x3_entry (csrc/conv.hip): in the split class a convolution with Cout % 128 == 0 && Cout % 256 != 0 (the pts3d
+# Twin of `big >= 224` in conv3x3_route (csrc/routes.h): in the split class a convolution with Cout % 128 == 0 && Cout % 256 != 0 (the pts3d
 # head's 256 -> 128) runs on a 256-pixel tile kernel, the only kind that reads a packed (hi, lo) input, from 224 tiles on -- so from this many
-# pixels on the trunk writes its last map packed.  If the two drift apart the library refuses the call ("a packed input is taken by the ...").
+# pixels on (in whole tiles) the trunk writes its last map packed.  tests/test_routes_cpu.py holds the two together over every batch and grid.
 PACKED_CONV_MIN_PIXELS = 224 * 256
 # K per tap of the fused conv3x3 -> 1x1 kernels in 2-byte units: `Cin == 64 << s` in vs_conv3x3_head1x1_nhwc (16-bit channels), `2 * Cin ==
 # 64 << s` in vs_conv3x3_head1x1_split_nhwc (f32 channels, two units each) -- ONE constraint: 64..512 16-bit or 32..256 f32 channels.
@@ -36,7 +36,7 @@ def pts3d_route(cls: str, BT: int, gh: int, gw: int, c_trunk: int, c_h0: int, c_
     """-> (route, trunk_packed: the trunk's last bilinear pass writes the packed (hi, lo) form) for operand class "f16" / "bf16" / "f32" / "split", BT
     frames of gh x gw tokens, the channels of the trunk, head[0] and head[2].  The head's 256 * BT * gh * gw pixels always fill 256-pixel tiles."""
     # head[0] then runs on the 256 x 128 tile kernel (conv3x3_entry: a whole, even number of K tiles); otherwise the trunk writes plain f32
-    trunk_packed = cls == "split" and c_h0 == 128 and c_trunk in (64, 128, 256) and BT * 64 * gh * gw >= PACKED_CONV_MIN_PIXELS
+    trunk_packed = cls == "split" and c_h0 == 128 and c_trunk in (64, 128, 256) and -(-BT * 64 * gh * gw // 256) * 256 >= PACKED_CONV_MIN_PIXELS
     if c_h0 == 128 and cls == "split" and c_h2 == 128:
         return "split_packed_dot", trunk_packed
     return ("fused16" if c_h0 == 128 and cls in ("f16", "bf16") else "unfused"), trunk_packed     # (no other one-kernel form: conv3x3, then a GEMM)
