@@ -7,5 +7,6 @@ The sub-packages mirror the reference's import surface:
     vicasplat_amd.diff_gaussian_rasterization   <- `diff_gaussian_rasterization` (cuda_splatting.py:5-8)
     vicasplat_amd.curope                        <- croco/curope (curope2d.py, curope.cpp)
     vicasplat_amd.model.encoder / .decoder      <- src/model/encoder, src/model/decoder
+    vicasplat_amd.dataset.shims                 <- src/dataset/shims (crop_shim, augmentation_shim)
 """
 __version__ = "0.1.0"
