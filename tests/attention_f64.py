@@ -16,6 +16,8 @@ from types import SimpleNamespace
 
 import torch
 
+from attention_route_cases import FAMILIES  # noqa: F401  (the input families: make_case keywords by name)
+
 HD = 64                      # head dimension of every attention kernel
 LN2 = math.log(2.0)
 STORAGE = {"f16": torch.float16, "bf16": torch.bfloat16, "f32": torch.float32}
@@ -243,32 +245,6 @@ def rel(a, b):
     a, b = a.double(), b.double().to(a.device)
     return float((a - b).abs().max() / (b.abs().max() + 1e-300))
 
-
-# The input families of tests/test_attention_routes_gpu.py: name -> make_case keywords (shape and storage are added per case).
-FAMILIES = {
-    "plain": dict(),
-    "ragged": dict(mask="ragged"),
-    "camera2": dict(mask="camera2"),
-    "camera3": dict(mask="camera3"),
-    "camera8": dict(mask="camera8"),
-    "seg_prod2": dict(seg="prod2"),
-    "seg_zero_first": dict(seg="zero_first"),
-    "seg_uneven": dict(seg="uneven"),
-    "seg_twice": dict(seg="twice"),
-    "seg_overlap": dict(seg="overlap"),
-    "seg_uneven_ragged": dict(seg="uneven", mask="ragged"),
-    "seg_prod2_ragged": dict(seg="prod2", mask="ragged"),
-    "plain_peaked": dict(regime="peaked"),
-    "ragged_peaked": dict(mask="ragged", regime="peaked"),
-    "seg_uneven_peaked": dict(seg="uneven", regime="peaked"),
-    "seg_uneven_ragged_peaked": dict(seg="uneven", mask="ragged", regime="peaked"),
-    "plain_uniform": dict(regime="uniform"),
-    "ragged_uniform": dict(mask="ragged", regime="uniform"),
-    "seg_uneven_ragged_uniform": dict(seg="uneven", mask="ragged", regime="uniform"),
-    "plain_scale03": dict(scale=0.3),
-    "ragged_scale03": dict(mask="ragged", scale=0.3),
-    "seg_uneven_ragged_scale03": dict(seg="uneven", mask="ragged", scale=0.3),
-}
 
 # Per storage class: (forward out, lse [log2 units], backward dq / dk / dv) -- the project's bounds (tests/test_ops_gpu.py,
 # test_split_path_gpu.py, test_split_bwd_gpu.py, test_f32_path_gpu.py); the 16-bit lse entries are the derived ceilings 2^-11 / ln 2 and

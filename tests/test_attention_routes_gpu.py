@@ -5,13 +5,12 @@ ctypes C ABI).  -m gpu.
 Operand classes: f16, bf16 (resident / 64-query / 128-query kernels; backward through the atomic entry and the direct 16-bit entry),
 f32x (the exact-f32 kernel, dtype 3, forward only), split (f32 in; f32 and packed out; split backward), sp (packed q | k | v in; f32 and
 packed out).  The route a case is meant to reach is the first part of its id:
-    res     attention_res_kernel          (16-bit, no mask / segments, Lk <= 320, Lq <= 384)
-    k1      attention_kernel<*,1>         (the resident route's exits, and every masked / segmented 16-bit case)
-    k2      attention_kernel<*,2>         (cdiv(Lq,128) * H * nbatch >= 512 and Lk > 1024)
-    split1  attention_split_kernel<1>,  split2  attention_split_kernel<2>  (same count and Lk > 256)
-    sp      attention_sp_kernel<3>        (96-query tiles)
-    sweep / fam: lengths across the tile edges and every input family of attention_f64.FAMILIES, all classes (16-bit: res when the
+    res     attention_res_kernel            k1      attention_kernel<*,1>           k2      attention_kernel<*,2>
+    split1  attention_split_kernel<1>       split2  attention_split_kernel<2>       sp      attention_sp_kernel<3>
+    sweep / fam: lengths across the tile edges and every input family of attention_route_cases.FAMILIES, all classes (16-bit: res when the
     case is plain and short, k1 otherwise; f32x: attention_f32_kernel).
+The thresholds between the routes are attention_route of csrc/routes.h; tests/test_routes_cpu.py proves on the CPU that every case of
+tests/attention_route_cases.py reaches the route its id names, and that every route is reached.
 Inputs come from attention_f64.make_case, whose planted boundary keys make a mask / segment / tile error move out, lse and the gradients
 by >= 10x every bound used here (asserted on the CPU in tests/test_attention_ref_cpu.py).
 
@@ -31,14 +30,14 @@ from types import SimpleNamespace
 import pytest
 import torch
 
-from attention_f64 import FAMILIES, LSE16_BOUND, STORAGE, attention_f64, make_case, rel
+from attention_f64 import LSE16_BOUND, STORAGE, attention_f64, make_case, rel
+from attention_route_cases import ALL, CASES, FAMILIES, PERMUTE_CASES
 
 pytestmark = pytest.mark.gpu
 
 TOL_OUT = {"f16": 3e-3, "bf16": 2e-2, "f32x": 3e-6, "split": 6e-6, "sp": 6e-6}
 TOL_LSE = {"f16": LSE16_BOUND["f16"], "bf16": LSE16_BOUND["bf16"], "f32x": 1e-4, "split": 1e-4, "sp": 1e-4}
 TOL_BWD = {"f16": 6e-3, "bf16": 3e-2, "split": 1e-5}
-ALL = ("f16", "bf16", "f32x", "split", "sp")
 SENTINEL = -1024.0          # exactly representable in f16 and bf16
 
 
@@ -180,41 +179,6 @@ def _check_case(cls, c, tag):
     return run, out, lse
 
 
-# ------------------------------------------------------------------------------------------------------------------------------------
-# cases: (id, classes, make_case keywords)
-# ------------------------------------------------------------------------------------------------------------------------------------
-def _cases():
-    cs = []
-    b16 = ("f16", "bf16")
-    for Lq, Lk in [(1, 1), (257, 16), (384, 17), (257, 257), (384, 320), (1, 320)]:
-        cs.append((f"res-Lq{Lq}-Lk{Lk}", b16, dict(nbatch=2, H=3, Lq=Lq, Lk=Lk)))
-    cs.append(("k1-exit-Lk321", b16, dict(nbatch=2, H=3, Lq=257, Lk=321)))
-    cs.append(("k1-exit-Lq385", b16, dict(nbatch=2, H=3, Lq=385, Lk=257)))
-    cs.append(("k1-exit-257-ragged", b16, dict(nbatch=2, H=3, Lq=257, mask="ragged")))
-    cs.append(("k1-exit-257-seg_prod2", b16, dict(nbatch=2, H=3, Lq=257, seg="prod2")))
-    cs.append(("k2-1032-H16-nb4-plain", b16, dict(nbatch=4, H=16, Lq=1032)))            # 9 * 16 * 4 = 576 work-groups, last query tile 8 rows
-    cs.append(("k2-1032-H16-nb4-camera8", b16, dict(nbatch=4, H=16, Lq=1032, mask="camera8")))
-    cs.append(("split2-257-H16-nb11-plain", ("split",), dict(nbatch=11, H=16, Lq=257)))    # 3 * 16 * 11 = 528
-    cs.append(("split2-257-H16-nb11-ragged", ("split",), dict(nbatch=11, H=16, Lq=257, mask="ragged")))
-    cs.append(("split2-516-H16-nb7-plain", ("split",), dict(nbatch=7, H=16, Lq=516)))      # 5 * 16 * 7 = 560
-    cs.append(("split1-257-H16-nb10-plain", ("split",), dict(nbatch=10, H=16, Lq=257)))    # 480: just below the count
-    for Lq in (1, 95, 96, 97, 257, 1032):
-        cs.append((f"sp-Lq{Lq}-plain", ("sp",), dict(nbatch=2, H=2, Lq=Lq)))
-    for Lq in (97, 1032):
-        cs.append((f"sp-Lq{Lq}-ragged", ("sp",), dict(nbatch=2, H=2, Lq=Lq, mask="ragged")))
-    for L in (1, 15, 16, 17, 63, 64, 65, 127, 128, 129, 255, 256, 258):
-        for fam in ("plain", "ragged", "seg_uneven"):
-            cs.append((f"sweep-L{L}-{fam}", ALL, dict(nbatch=2, H=2, Lq=L, **FAMILIES[fam])))
-    for Lq, Lk in ((1, 300), (300, 1)):
-        for fam in ("plain", "ragged"):
-            cs.append((f"sweep-Lq{Lq}-Lk{Lk}-{fam}", ALL, dict(nbatch=2, H=2, Lq=Lq, Lk=Lk, **FAMILIES[fam])))
-    for L in (100, 257):
-        for fam, kw in FAMILIES.items():
-            cs.append((f"fam-L{L}-{fam}", ALL, dict(nbatch=3, H=2, Lq=L, **kw)))
-    return cs
-
-
-CASES = _cases()
 PARAMS = [pytest.param(cls, kw, id=f"{cid}-{cls}") for cid, classes, kw in CASES for cls in classes]
 
 
@@ -253,10 +217,7 @@ def test_padded_batch_rows_do_not_leak(cls, L, fam, request):
             assert torch.equal(a[live], b)
 
 
-@pytest.mark.parametrize("cid,cls,kw", [("sp-257-H4-nb8", "sp", dict(nbatch=8, H=4, Lq=257)),
-                                        ("sp-96-H2-nb5-ragged", "sp", dict(nbatch=5, H=2, Lq=96, mask="ragged")),
-                                        ("k2-1032-H16-nb4", "f16", dict(nbatch=4, H=16, Lq=1032)),
-                                        ("split2-257-H16-nb11", "split", dict(nbatch=11, H=16, Lq=257, mask="ragged"))])
+@pytest.mark.parametrize("cid,cls,kw", PERMUTE_CASES)
 def test_permuting_batch_items_permutes_the_result(cid, cls, kw):
     """An XCD / grid remap that crossed batch items would not survive this: the items in another order give the same bits in that order."""
     c = make_case(seed=7, storage=_storage(cls), **kw)

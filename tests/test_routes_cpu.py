@@ -1,11 +1,15 @@
-"""The forward route functions of vicasplat_amd/csrc/routes.h (gemm_plan, conv3x3_route), compiled for the host and run without a GPU.
+"""The route functions of vicasplat_amd/csrc/routes.h (gemm_plan, conv3x3_route, attention_route, attention_bwd_route, xcd_remap), compiled
+for the host and run without a GPU.
 
-tests/route_probe.cpp is built once per session with the host compiler; the tests then hold the header to its three restatements:
+tests/route_probe.cpp is built once per session with the host compiler; the tests then hold the header to its restatements:
   * tests/gemm_f64.py plan(), which names the routes of the GPU GEMM tests (there may be no compiler where those run): string for string
     over a grid of every class, epilogue, packing and M at every tile edge; and under VS_DETERMINISTIC no plan splits K;
   * the halo column of tests/test_conv_halo_gpu.py CASES and a table of pinned convolution shapes, one at least per route kind;
   * PACKED_CONV_MIN_PIXELS of model/encoder/heads/dpt.py: the trunk writes its last map packed exactly where the head's first convolution
-    reads a packed input (the 256 x 128 tile kernel), and never where the library would refuse one.
+    reads a packed input (the 256 x 128 tile kernel), and never where the library would refuse one;
+  * the ids of tests/attention_route_cases.py: every GPU attention case reaches the route its id names, every route is reached, and a table
+    of pinned shapes sits on both sides of every attention threshold;
+  * xcd_remap is a permutation of [0, n) that hands every XCD one contiguous range of logical ids, for every grid size tried.
 """
 import os
 import shutil
@@ -14,6 +18,7 @@ import subprocess
 import pytest
 
 import gemm_f64
+from attention_route_cases import CASES as ATTN_CASES, PERMUTE_CASES
 from test_conv_halo_gpu import CASES as HALO_CASES
 from vicasplat_amd.model.encoder.heads.dpt import pts3d_route
 
@@ -154,3 +159,76 @@ def test_trunk_writes_packed_exactly_where_the_head_convolution_reads_it(probe):
         assert not (trunk_packed and r == "packed_not_taken")
         packed += trunk_packed
     assert 0 < packed < len(shapes)
+
+
+# ---- attention -----------------------------------------------------------------------------------------------------------------------
+ATTN_ROUTE_OF_PREFIX = {"res": "res", "k1": "tile64", "k2": "tile128", "split1": "split64", "split2": "split128", "sp": "sp"}
+ATTN_KINDS = ("res", "tile64", "tile128", "f32", "split64", "split128", "sp")
+
+
+def _attn_query(cls, kw):
+    """What make_case hands the ABI for these keywords: Lk = Lq when none is given; with key segments Lk = 0 and the lengths in kv_seg."""
+    seg, masked = kw.get("seg") is not None, kw.get("mask", "none") != "none"
+    Lk = 0 if seg else kw.get("Lk", kw["Lq"])
+    return "a %s %d %d %d %d %d %d" % (cls, kw["nbatch"], kw["H"], kw["Lq"], Lk, seg, masked)
+
+
+def _attn_expected(cid, cls, kw):
+    prefix = cid.split("-")[0]
+    if prefix in ATTN_ROUTE_OF_PREFIX:
+        return ATTN_ROUTE_OF_PREFIX[prefix]
+    assert prefix in ("sweep", "fam"), cid
+    if cls in ("f16", "bf16"):
+        plain = kw.get("seg") is None and kw.get("mask", "none") == "none"
+        return "res" if plain and kw.get("Lk", kw["Lq"]) <= 320 and kw["Lq"] <= 384 else "tile64"
+    return {"f32x": "f32", "split": "split64", "sp": "sp"}[cls]
+
+
+def test_every_gpu_attention_case_reaches_the_route_its_id_names(probe):
+    cases = [(cid, cls, kw) for cid, classes, kw in ATTN_CASES for cls in classes] + list(PERMUTE_CASES)
+    got = [g.split()[0] for g in probe([_attn_query(cls, kw) for _, cls, kw in cases])]
+    want = [_attn_expected(cid, cls, kw) for cid, cls, kw in cases]
+    assert got == want, [(c[0], c[1], g, w) for c, g, w in zip(cases, got, want) if g != w]
+    assert set(got) == set(ATTN_KINDS), set(ATTN_KINDS) - set(got)
+
+
+# (class, nbatch, H, Lq, Lk, has_seg, has_len) -> the route, worked out by hand from the thresholds: resident up to 320 keys and 384 queries
+# without mask or segments; 128-query tiles from 512 workgroups of them and Lk_eff > 1024 (16-bit) / > 256 (split), Lk_eff = 2 Lk with segments
+ATTN_PINS = [
+    (("f16", 2, 3, 384, 320, 0, 0), "res grid=1x3x2 block=512"),
+    (("f16", 2, 3, 384, 321, 0, 0), "tile64 grid=6x3x2"),
+    (("f16", 2, 3, 385, 320, 0, 0), "tile64 grid=7x3x2"),
+    (("f16", 2, 3, 384, 320, 0, 1), "tile64 grid=6x3x2"),
+    (("f16", 4, 16, 1024, 1025, 0, 0), "tile128 grid=8x16x4"),          # exactly 512 workgroups
+    (("f16", 4, 16, 1024, 1024, 0, 0), "tile64 grid=16x16x4"),
+    (("f16", 3, 16, 1032, 1032, 0, 0), "tile64 grid=17x16x3"),          # 432 workgroups of 128 queries
+    (("split", 11, 16, 257, 257, 0, 0), "split128 grid=3x16x11"),       # 528
+    (("split", 11, 16, 257, 256, 0, 0), "split64 grid=5x16x11"),
+    (("split", 10, 16, 257, 257, 0, 0), "split64 grid=5x16x10"),        # 480
+    (("split", 11, 16, 257, 129, 1, 0), "split128 grid=3x16x11"),       # Lk_eff = 258
+    (("split", 11, 16, 257, 0, 1, 0), "split64 grid=5x16x11"),          # what every caller passes with segments
+]
+
+
+def test_pinned_attention_shapes_take_their_route(probe):
+    got = probe(["a %s %d %d %d %d %d %d" % s for s, _ in ATTN_PINS])
+    assert got == [r for _, r in ATTN_PINS], [(s, g, r) for (s, r), g in zip(ATTN_PINS, got) if g != r]
+    lqs = (1, 95, 96, 97, 1032)
+    assert probe(["a sp 2 2 %d %d 0 0" % (L, L) for L in lqs]) == ["sp grid=%d" % n for n in (4, 4, 4, 8, 44)]
+
+
+def test_backward_grids(probe):
+    """keys = max_keys under segments, Lk otherwise; dq in 128-query tiles; dk|dv in 128-key (16-bit) / 64-key (split) tiles."""
+    q = ["b 16 257 257 0 0", "b 16 257 0 1 514", "b split 257 257 0 0", "b split 129 0 1 65", "b 16 128 128 0 0", "b split 128 64 0 0"]
+    assert probe(q) == ["keys=257 dq=3 dkv=3", "keys=514 dq=3 dkv=5", "keys=257 dq=3 dkv=5", "keys=65 dq=2 dkv=2", "keys=128 dq=1 dkv=1",
+                        "keys=64 dq=1 dkv=1"]
+
+
+def test_xcd_remap_is_a_permutation_with_one_range_per_xcd(probe):
+    """Otherwise two workgroups would compute one tile and one tile would never be computed, or the tiles of one XCD would not be neighbours."""
+    ns = set(range(1, 4097)) | {256 * k + d for k in range(1, 65) for d in (-1, 0, 1)}
+    # grids of the 8-scene bench step: 96-query tiles x 16 heads x 192 frames; 256-pixel conv tiles of 192 maps of 64 x 64; 2^20 rows / 256
+    ns |= {3 * 16 * 192, 3 * 12 * 192, 22 * 16 * 24, 3072, 12288, 4096 * 3, 65535, 1 << 20}
+    ns = sorted(ns)
+    got = probe(["x %d" % n for n in ns])
+    assert got == ["ok"] * len(ns), [(n, g) for n, g in zip(ns, got) if g != "ok"][:5]

@@ -15,62 +15,14 @@
 // (S^T = K Q^T with v_mfma_f32_16x16x32) so that every lane owns ONE query column: the online-softmax row
 // reductions are 15 in-register max/adds + 2 cross-lane steps, and the f32->16-bit P fragments are already in
 // the A-operand layout of the P.V MFMA (keys permuted consistently on the V side).
-#include "common.h"
+#include "attention_common.h"
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-constexpr int HD = 64;       // head dim
 constexpr int KB = 64;       // keys per tile
 constexpr int KROW = HD + 8; // halfs, K tile row stride (144 B)
 
-struct AttnArgs {
-    const unsigned short *q, *k, *v;
-    unsigned short *out;
-    const int32_t *kv_seg;   // [nbatch,4] base0,len0,base1,len1 (rows) or null
-    const int32_t *q_kvlen;  // [nbatch*Lq] or null
-    int nbatch, H, Lq, Lk;
-    long long q_batch_rows, k_batch_rows;
-    int ldq, ldk, ldv, ldo;
-    float scale_log2e;
-    float *lse;  // optional [rows, H] f32: log2-domain logsumexp of the scaled scores (saved for the backward pass)
-};
-
-template <bool BF16>
-__device__ __forceinline__ f4 mfma(const uint4 &a, const uint4 &b, f4 c) {
-    if constexpr (BF16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf8 *>(&a), *reinterpret_cast<const bf8 *>(&b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const half8 *>(&a), *reinterpret_cast<const half8 *>(&b), c, 0, 0, 0);
-}
-
-template <bool BF16>
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-    // one packed convert (round to nearest even) instead of two converts + an OR: the softmax / dS path is VALU-bound
-    unsigned r;
-    if constexpr (BF16) asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    else asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
-// The same convert for a value that goes STRAIGHT INTO AN MFMA: compiler-visible instructions, so that the hazard recogniser inserts the
-// VALU-write -> MFMA-read wait states (it does not look inside inline asm).  Round 4: attention_sp_kernel's third query group came out
-// 5e-5 off with the asm form whenever the scheduler placed a P V MFMA right behind the convert; the older kernels used the asm form for
-// their P fragments too and were only protected by what happened to be scheduled in between.
-template <bool BF16>
-__device__ __forceinline__ unsigned pack2v(float a, float b) {
-    typedef float f2p_ __attribute__((ext_vector_type(2)));
-    if constexpr (BF16) {
-        typedef __bf16 b2p_ __attribute__((ext_vector_type(2)));
-        return __builtin_bit_cast(unsigned, __builtin_convertvector(f2p_{a, b}, b2p_));
-    } else {
-        typedef _Float16 h2p_ __attribute__((ext_vector_type(2)));
-        return __builtin_bit_cast(unsigned, __builtin_convertvector(f2p_{a, b}, h2p_));
-    }
-}
+typedef AttnArgs<unsigned short> AttnArgs16;
 
 template <bool BF16>
 __device__ __forceinline__ unsigned short to16(float v) {
@@ -166,19 +118,18 @@ __device__ __forceinline__ void softmax_tile(f4 (&st)[4], float scale_log2e, flo
 // &tile[row0 + (t >> 2)][col0 + (t & 3) * 4] and receives tile[row0 .. row0 + 3][col0 + t].  With it the P V product reads V as it is
 // staged (16-byte row copies): no transposed V image, whose staging cost eight 4-byte LDS stores and ~16 bit operations per thread and
 // tile (cycle stamps: 24 % of a frame-encoder workgroup's time was K/V staging).
-typedef short tr4v_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint2 v_rows4(const unsigned short *tile, int row0, int col0, int t) {
-    typedef tr4v_t __attribute__((address_space(3))) *trp_t;
+    typedef tr4_t __attribute__((address_space(3))) *trp_t;
     const unsigned short *p = tile + (row0 + (t >> 2)) * KROW + col0 + (t & 3) * 4;
-    const tr4v_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((trp_t)(const_cast<unsigned short *>(p)));
+    const tr4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((trp_t)(const_cast<unsigned short *>(p)));
     return __builtin_bit_cast(uint2, v);
 }
 
 template <int PITCH>
 __device__ __forceinline__ uint2 v_rows4p(const unsigned short *tile, int row0, int col0, int t) {   // v_rows4 on rows of PITCH halves
-    typedef tr4v_t __attribute__((address_space(3))) *trp_t;
+    typedef tr4_t __attribute__((address_space(3))) *trp_t;
     const unsigned short *p = tile + (row0 + (t >> 2)) * PITCH + col0 + (t & 3) * 4;
-    const tr4v_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((trp_t)(const_cast<unsigned short *>(p)));
+    const tr4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((trp_t)(const_cast<unsigned short *>(p)));
     return __builtin_bit_cast(uint2, v);
 }
 
@@ -208,7 +159,7 @@ __device__ __forceinline__ void store_o_rows(const f4 (&o)[4], float l, int q, i
 
 // occupancy target (waves per EU): 3 for 128-query workgroups, 4 for 64-query ones
 template <bool BF16, int QG>
-__global__ void __launch_bounds__(256, QG == 2 ? 3 : 4) attention_kernel(const AttnArgs a) {
+__global__ void __launch_bounds__(256, QG == 2 ? 3 : 4) attention_kernel(const AttnArgs16 a) {
     constexpr int QBLK = 64 * QG;
     __shared__ __attribute__((aligned(16))) unsigned short sK2[2][KB * KROW];   // two-tile ring: one barrier per tile
     __shared__ __attribute__((aligned(16))) unsigned short sV2[2][KB * KROW];    // row-major, read through ds_read_b64_tr_b16
@@ -217,13 +168,7 @@ __global__ void __launch_bounds__(256, QG == 2 ? 3 : 4) attention_kernel(const A
     const int g = lane >> 4, c16 = lane & 15;
     const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * QBLK;
 
-    int base0, len0, base1, len1;
-    if (a.kv_seg) {
-        base0 = a.kv_seg[4 * b + 0]; len0 = a.kv_seg[4 * b + 1]; base1 = a.kv_seg[4 * b + 2]; len1 = a.kv_seg[4 * b + 3];
-    } else {
-        base0 = (int)(b * a.k_batch_rows); len0 = a.Lk; base1 = 0; len1 = 0;
-    }
-    const int Lk = len0 + len1;
+    const KeyList kl = key_list(a, b);
 
     // ---- this lane's queries (columns of S^T): one per 16-query group ----
     int my_len[QG];
@@ -234,9 +179,7 @@ __global__ void __launch_bounds__(256, QG == 2 ? 3 : 4) attention_kernel(const A
         const int qi = q0 + (wid * QG + u) * 16 + c16;
         const bool qvalid = qi < a.Lq;
         const long long qrow = b * a.q_batch_rows + (qvalid ? qi : a.Lq - 1);
-        int ml = Lk;
-        if (a.q_kvlen && qvalid) ml = min(Lk, a.q_kvlen[(long long)b * a.Lq + qi]);
-        if (!qvalid) ml = 0;
+        const int ml = query_len(a, kl, b, qi, qvalid);
         my_len[u] = ml;
         wave_len = max(wave_len, ml);
         const unsigned short *qp = a.q + qrow * a.ldq + h * HD + g * 8;
@@ -271,16 +214,12 @@ __global__ void __launch_bounds__(256, QG == 2 ? 3 : 4) attention_kernel(const A
     // staging roles
     const int k_key = tid >> 2, k_chunk = (tid & 3) * 16;  // K and V: one key row, 2 x 16B of it
 
-    auto key_row = [&](int j) -> long long {
-        j = min(j, Lk - 1);
-        return j < len0 ? (long long)base0 + j : (long long)base1 + (j - len0);
-    };
     uint4 pk0, pk1, pva, pvb;  // register prefetch of the NEXT tile (hides the global latency behind the MFMAs)
     auto gload = [&](int kt) {
-        const unsigned short *kp = a.k + key_row(kt + k_key) * a.ldk + h * HD + k_chunk;
+        const unsigned short *kp = a.k + kl.row(kt + k_key) * a.ldk + h * HD + k_chunk;
         pk0 = *reinterpret_cast<const uint4 *>(kp);
         pk1 = *reinterpret_cast<const uint4 *>(kp + 8);
-        const unsigned short *vp = a.v + key_row(kt + k_key) * a.ldv + h * HD + k_chunk;
+        const unsigned short *vp = a.v + kl.row(kt + k_key) * a.ldv + h * HD + k_chunk;
         pva = *reinterpret_cast<const uint4 *>(vp);
         pvb = *reinterpret_cast<const uint4 *>(vp + 8);
     };
@@ -367,10 +306,9 @@ __global__ void __launch_bounds__(256, QG == 2 ? 3 : 4) attention_kernel(const A
 // all keys and values go to LDS once (both row-major, 76.5 KiB for 272 padded keys -> two workgroups per CU),
 // one barrier, then every wave walks its 16-query groups over the key tiles with no further synchronisation; a partial
 // last tile only runs the 16-key sub-blocks that hold keys. ----
-constexpr int kResMaxKeys = 320;
 
 template <bool BF16>
-__global__ void __launch_bounds__(512, 2) attention_res_kernel(const AttnArgs a) {
+__global__ void __launch_bounds__(512, 2) attention_res_kernel(const AttnArgs16 a) {
     extern __shared__ __attribute__((aligned(16))) unsigned short smem_res[];
     const int Lk = a.Lk;
     const int Lkp = (Lk + 15) & ~15;      // keys padded to the 16-key MFMA sub-block
@@ -383,7 +321,7 @@ __global__ void __launch_bounds__(512, 2) attention_res_kernel(const AttnArgs a)
 
     // ---- stage all keys / values: thread -> (key, 16-half chunk) for K, (key pair, 8-dim chunk) for V.  Every global
     // load of the workgroup is issued before the first LDS store (up to 3 rounds x 4 x 16 B per thread in flight). ----
-    constexpr int NR = (kResMaxKeys * 4 + 511) / 512;  // rounds of 512 threads over (key, 16-half chunk) items
+    constexpr int NR = (vs::route::kResMaxKeys * 4 + 511) / 512;  // rounds of 512 threads over (key, 16-half chunk) items
     uint4 rk[NR][2], rv[NR][2];
     const int nK = Lkp * 4;
 #pragma unroll
@@ -489,17 +427,7 @@ __global__ void __launch_bounds__(512, 2) attention_res_kernel(const AttnArgs a)
 // is three f16 MFMAs on (hi, lo) pairs -- hi = rne16(x), lo = rne16(x - hi) -- with f32 accumulation: f32-class results at a third of
 // the 16-bit matrix rate instead of the 1/16 of the exact-f32 MFMA.  Same structure, masks and segments as attention_kernel: the K / V
 // tiles are converted once when they are staged (two LDS images each), Q when it is loaded, P in registers after the exponentials. ----
-struct AttnArgsSplit {
-    const float *q, *k, *v;
-    float *out;
-    const int32_t *kv_seg, *q_kvlen;
-    int nbatch, H, Lq, Lk;
-    long long q_batch_rows, k_batch_rows;
-    int ldq, ldk, ldv, ldo;
-    float scale_log2e;
-    float *lse;
-    int out_packed;   // write O in the packed (hi, lo) form of the split class (the A operand of the projection GEMM: vs_gemm_split_packed)
-};
+typedef AttnArgs<float> AttnArgsF;
 
 // four consecutive columns n .. n + 3 of an f32 row written in the packed (hi, lo) layout of vs_split_pack_weight (gemm_common.h, store_split4)
 // The residuals x - hi are taken from the f32 values as given: no contraction with the producer of a .. d (an fma would subtract hi from
@@ -540,7 +468,7 @@ __device__ __forceinline__ f4 mma3(const uint4 &bh, const uint4 &bl, const uint4
 }
 
 template <int QG>
-__global__ void __launch_bounds__(256, 2) attention_split_kernel(const AttnArgsSplit a) {
+__global__ void __launch_bounds__(256, 2) attention_split_kernel(const AttnArgsF a) {
     constexpr int QBLK = 64 * QG;
     __shared__ __attribute__((aligned(16))) unsigned short sKh2[2][KB * KROW], sKl2[2][KB * KROW];   // two-tile ring, hi / lo images
     // V tiles keep the K pitch (144 B).  A 160-byte pitch (the four rows of a transpose read in four disjoint 8-bank windows) was measured:
@@ -550,8 +478,9 @@ __global__ void __launch_bounds__(256, 2) attention_split_kernel(const AttnArgsS
     __shared__ int s_maxlen;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int g = lane >> 4, c16 = lane & 15;
-    // XCD-aware (tile, head, batch) ids: consecutive workgroups are dealt to consecutive XCDs, so make consecutive LOGICAL ids share one
-    // (gemm256_kernel's remap): the query tiles of one (batch, head) read its K / V behind ONE L2 (attention_bwd.hip block_bhx)
+    // XCD-aware (tile, head, batch) ids, as attention_bwd.hip block_bhx: the query tiles of one (batch, head) read its K / V behind ONE L2.  (The
+    // remap stays written out here, on shifts: through xcd_remap's divisions the compiler orders a few instructions of the tile loop differently.
+    // This is the project's one copy of routes.h xcd_remap, under other variable names: a change there is repeated here.)
     int b, h, bx_;
     {
         const int gx = gridDim.x, gy = gridDim.y, n = gx * gy * gridDim.z;
@@ -562,13 +491,9 @@ __global__ void __launch_bounds__(256, 2) attention_split_kernel(const AttnArgsS
     }
     const int q0 = bx_ * QBLK;
 
-    int base0, len0, base1, len1;
-    if (a.kv_seg) {
-        base0 = a.kv_seg[4 * b + 0]; len0 = a.kv_seg[4 * b + 1]; base1 = a.kv_seg[4 * b + 2]; len1 = a.kv_seg[4 * b + 3];
-    } else {
-        base0 = (int)(b * a.k_batch_rows); len0 = a.Lk; base1 = 0; len1 = 0;
-    }
-    const int Lk = len0 + len1;
+    const KeyList kl = key_list(a, b);
+    // (this kernel keeps the list in locals and its own row lookup: through kl.row() the compiler schedules the staging loads differently)
+    const int base0 = kl.base0, len0 = kl.len0, base1 = kl.base1, Lk = kl.Lk;
 
     int my_len[QG];
     uint4 qh[QG][2], ql[QG][2];
@@ -578,9 +503,7 @@ __global__ void __launch_bounds__(256, 2) attention_split_kernel(const AttnArgsS
         const int qi = q0 + (wid * QG + u) * 16 + c16;
         const bool qvalid = qi < a.Lq;
         const long long qrow = b * a.q_batch_rows + (qvalid ? qi : a.Lq - 1);
-        int ml = Lk;
-        if (a.q_kvlen && qvalid) ml = min(Lk, a.q_kvlen[(long long)b * a.Lq + qi]);
-        if (!qvalid) ml = 0;
+        const int ml = query_len(a, kl, b, qi, qvalid);
         my_len[u] = ml;
         wave_len = max(wave_len, ml);
         const float *qp = a.q + qrow * a.ldq + h * HD + g * 8;
@@ -735,7 +658,7 @@ __global__ void __launch_bounds__(256, 2) attention_split_kernel(const AttnArgsS
 // 4 + 16: per block of 32 columns 32 hi halves then 32 lo halves, gemm_common.h store_split4), so a head's row of q, k or v is 256 bytes =
 // [hi 0..31 | lo 0..31 | hi 32..63 | lo 32..63] (positions; the column order inside a block is the packed permutation, the same for q and
 // k, so dot products need no un-permutation, and V's column position IS the output's packed position).  What that buys here:
-//   * staging is plain LDS-DMA (global_load_lds_dwordx4): no conversion VALU, no staging registers, the next tile in flight under the
+//   * staging is plain LDS-DMA (glds16): no conversion VALU, no staging registers, the next tile in flight under the
 //     current tile's MFMAs, one barrier per tile.  attention_split_kernel converted every K / V tile again in EVERY workgroup that
 //     staged it (17 x for the 2064-key video attention);
 //   * LDS read traffic per FLOP is HALVED: PMC on attention_split_kernel showed the LDS pipe as its busiest unit (47 % + 20 % conflict
@@ -749,23 +672,21 @@ __global__ void __launch_bounds__(256, 2) attention_split_kernel(const AttnArgsS
 // LDS tiles are unpadded 256-byte rows; 16-byte chunk index XOR (key & 15) for K (conflict-free ds_read_b128 over 16 keys), 32-byte
 // chunk index XOR (key & 7) for V (the four rows of a ds_read_b64_tr_b16 in four different 32-byte windows); the swizzle is applied on
 // the GLOBAL side of the DMA.  Rows past the end of the key list are duplicates of the last key, masked by the length logic.
+// (its own block, not the common one plus members: with the kernarg layout of AttnArgs<float> + strides the compiler schedules this kernel's
+// tile loop differently; the host copies the common fields over)
 struct AttnArgsSP {
-    const unsigned char *q, *k, *v;   // packed rows; strides in bytes
+    const unsigned char *q, *k, *v;   // packed rows
     float *out;
     const int32_t *kv_seg, *q_kvlen;
-    int nbatch, H, Lq, Lk, nqt;
+    int nbatch, H, Lq, Lk, nqt;       // nqt: 96-query tiles per (batch, head)
     long long q_batch_rows, k_batch_rows;
-    long long ldq_b, ldk_b, ldv_b;
+    long long ldq_b, ldk_b, ldv_b;    // strides in bytes
     int ldo;
     float scale_log2e;
     float *lse;
     int out_packed;
 };
 
-typedef void __attribute__((address_space(3))) *lds_ptr_sp_t;
-__device__ __forceinline__ void glds16_sp(const void *gp, unsigned lds_off) {   // (inline asm: the compiler adds no waits of its own)
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds_off), "v"(gp) : "memory");
-}
 
 // online-softmax step of one 16-query group over this wave's 32 keys of a tile (softmax_tile for two 16-key blocks).  VALU work does NOT
 // hide under MFMAs on gfx950 (tools/probe/mfma_valu_overlap.hip: an MFMA-only wave and an FMA-only wave sharing a SIMD take the SUM of
@@ -869,7 +790,7 @@ __device__ __forceinline__ void sp_tile(const unsigned char *sK, const unsigned 
     }
     // ---- O^T += V^T P^T over the wave's 32 keys: V fragments through the transpose read, once for the four query groups.
     // db = 16-position block of the head's packed row: (db >> 1) = 32-column block, (db & 1) = its first / second 16 positions
-    typedef tr4v_t __attribute__((address_space(3))) *trp_t;
+    typedef tr4_t __attribute__((address_space(3))) *trp_t;
     auto trd = [&](int ofs) -> uint2 {
         return __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((trp_t)(const_cast<unsigned char *>(sV + ofs))));
     };
@@ -896,22 +817,14 @@ __global__ void __launch_bounds__(256, 2) attention_sp_kernel(const AttnArgsSP a
     const int qh = wid >> 1, kh = wid & 1;
     // ---- XCD-aware linear block id -> (batch, head, query tile): consecutive logical ids (one (batch, head)'s query tiles) share an XCD
     const int nwg = a.nqt * a.H * a.nbatch;
-    int bid = blockIdx.x;
-    {
-        const int qn = nwg / 8, r = nwg % 8, xcd = bid % 8, idx = bid / 8;
-        bid = (xcd < r ? xcd * (qn + 1) : r * (qn + 1) + (xcd - r) * qn) + idx;
-    }
+    const int bid = vs::route::xcd_remap(blockIdx.x, nwg);
     const int qt = bid % a.nqt, h = (bid / a.nqt) % a.H, b = bid / (a.nqt * a.H);
     const int q0 = qt * (2 * QW) + qh * QW;
-    const unsigned lds0 = (unsigned)(size_t)(lds_ptr_sp_t)&smem[0][0][0];
+    const unsigned lds0 = (unsigned)(size_t)(lds_ptr_t)&smem[0][0][0];
 
-    int base0, len0, base1, len1;
-    if (a.kv_seg) {
-        base0 = a.kv_seg[4 * b + 0]; len0 = a.kv_seg[4 * b + 1]; base1 = a.kv_seg[4 * b + 2]; len1 = a.kv_seg[4 * b + 3];
-    } else {
-        base0 = (int)(b * a.k_batch_rows); len0 = a.Lk; base1 = 0; len1 = 0;
-    }
-    const int Lk = len0 + len1;
+    const KeyList kl = key_list(a, b);
+    // (locals and its own row lookup, as attention_split_kernel: through kl the compiler schedules the tile loop differently)
+    const int base0 = kl.base0, len0 = kl.len0, base1 = kl.base1, Lk = kl.Lk;
 
     // ---- Q fragments: straight from the packed rows (hi chunk g, lo chunk g of the head's two 32-column blocks)
     int my_len[NG];
@@ -922,9 +835,7 @@ __global__ void __launch_bounds__(256, 2) attention_sp_kernel(const AttnArgsSP a
         const int qi = q0 + u * 16 + c16;
         const bool qvalid = qi < a.Lq;
         const long long qrow = b * a.q_batch_rows + (qvalid ? qi : a.Lq - 1);
-        int ml = Lk;
-        if (a.q_kvlen && qvalid) ml = min(Lk, a.q_kvlen[(long long)b * a.Lq + qi]);
-        if (!qvalid) ml = 0;
+        const int ml = query_len(a, kl, b, qi, qvalid);
         my_len[u] = ml;
         wave_len = max(wave_len, ml);
         wave_min = min(wave_min, ml);
@@ -991,15 +902,15 @@ __global__ void __launch_bounds__(256, 2) attention_sp_kernel(const AttnArgsSP a
             const unsigned char *kp = kbase + (rowbase + r0) * a.ldk_b, *vp = vbase + (rowbase + r0) * a.ldv_b;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                glds16_sp(kp + (long long)j * 16 * a.ldk_b, __builtin_amdgcn_readfirstlane(ldsk + (unsigned)j * 4096u));
-                glds16_sp(vp + (long long)j * 16 * a.ldv_b, __builtin_amdgcn_readfirstlane(ldsv + (unsigned)j * 4096u));
+                glds16(kp + (long long)j * 16 * a.ldk_b, __builtin_amdgcn_readfirstlane(ldsk + (unsigned)j * 4096u));
+                glds16(vp + (long long)j * 16 * a.ldv_b, __builtin_amdgcn_readfirstlane(ldsv + (unsigned)j * 4096u));
             }
         } else {                                 // a tile that straddles the segment boundary or the end of the list: per-row lookup
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const long long r = key_row(kt + j * 16 + r0);
-                glds16_sp(kbase + r * a.ldk_b, __builtin_amdgcn_readfirstlane(ldsk + (unsigned)j * 4096u));
-                glds16_sp(vbase + r * a.ldv_b, __builtin_amdgcn_readfirstlane(ldsv + (unsigned)j * 4096u));
+                glds16(kbase + r * a.ldk_b, __builtin_amdgcn_readfirstlane(ldsk + (unsigned)j * 4096u));
+                glds16(vbase + r * a.ldv_b, __builtin_amdgcn_readfirstlane(ldsv + (unsigned)j * 4096u));
             }
         }
     };
@@ -1104,26 +1015,13 @@ __global__ void __launch_bounds__(256, 2) attention_sp_kernel(const AttnArgsSP a
 // LDS -- runs the frame encoder's 257 x 257 attention at the same 28 ms per step as this tiled kernel: the time is the per-group softmax /
 // split VALU work and the 3 x MFMAs, not the re-staging.)
 
-}  // namespace
-
 // ---- reference-precision attention (f32 q | k | v and output, exact f32 MFMA v_mfma_f32_16x16x4_f32; DESIGN 2 "f32 path") ----
 // Same semantics and indexing as attention_kernel (key segments, per-query key-prefix lengths, log2-domain logsumexp), a plain
 // structure: 4 waves x 16 queries per workgroup, 32-key tiles of K and V staged synchronously in LDS (rows padded to 68 floats:
 // conflict-free float4 / float fragment reads), S^T = K Q^T so that a lane owns one query column, online softmax in f32, O += P V
 // with the scores used as the A operand as they are.  Summation index maps: QK^T step (j, s) takes d = 16 j + 4 g + s for both
 // operands (g = lane >> 4); P V step (nb, r) takes key = 16 nb + 4 g + r.
-struct AttnArgsF32 {
-    const float *q, *k, *v;
-    float *out;
-    const int32_t *kv_seg, *q_kvlen;
-    int nbatch, H, Lq, Lk;
-    long long q_batch_rows, k_batch_rows;
-    int ldq, ldk, ldv, ldo;
-    float scale_log2e;
-    float *lse;
-};
-
-__global__ void __launch_bounds__(256) attention_f32_kernel(const AttnArgsF32 a) {
+__global__ void __launch_bounds__(256) attention_f32_kernel(const AttnArgsF a) {
     constexpr int TK = 32, ROW = HD + 4;
     __shared__ __attribute__((aligned(16))) float sK[TK * ROW];
     __shared__ __attribute__((aligned(16))) float sV[TK * ROW];
@@ -1131,19 +1029,11 @@ __global__ void __launch_bounds__(256) attention_f32_kernel(const AttnArgsF32 a)
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int g = lane >> 4, c16 = lane & 15;
     const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * 64;
-    int base0, len0, base1, len1;
-    if (a.kv_seg) {
-        base0 = a.kv_seg[4 * b + 0]; len0 = a.kv_seg[4 * b + 1]; base1 = a.kv_seg[4 * b + 2]; len1 = a.kv_seg[4 * b + 3];
-    } else {
-        base0 = (int)(b * a.k_batch_rows); len0 = a.Lk; base1 = 0; len1 = 0;
-    }
-    const int Lk = len0 + len1;
+    const KeyList kl = key_list(a, b);
     const int qi = q0 + wid * 16 + c16;
     const bool qvalid = qi < a.Lq;
     const long long qrow = b * a.q_batch_rows + (qvalid ? qi : a.Lq - 1);
-    int my_len = Lk;
-    if (a.q_kvlen && qvalid) my_len = min(Lk, a.q_kvlen[(long long)b * a.Lq + qi]);
-    if (!qvalid) my_len = 0;
+    const int my_len = query_len(a, kl, b, qi, qvalid);
     float4 qf[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) qf[j] = *reinterpret_cast<const float4 *>(a.q + qrow * a.ldq + h * HD + 16 * j + 4 * g);
@@ -1160,14 +1050,10 @@ __global__ void __launch_bounds__(256) attention_f32_kernel(const AttnArgsF32 a)
 #pragma unroll
     for (int i = 0; i < 4; ++i) o[i] = f4{0.f, 0.f, 0.f, 0.f};
     float m_run = -INFINITY, l_run = 0.f;
-    auto key_row = [&](int j) -> long long {
-        j = min(j, Lk - 1);
-        return j < len0 ? (long long)base0 + j : (long long)base1 + (j - len0);
-    };
     const int s_key = tid >> 3, s_c = (tid & 7) * 8;   // staging: one key row, 8 floats of K and of V per thread
     for (int kt = 0; kt < maxlen; kt += TK) {
         {
-            const long long r = key_row(kt + s_key);
+            const long long r = kl.row(kt + s_key);
             const float *kp = a.k + r * a.ldk + h * HD + s_c, *vp = a.v + r * a.ldv + h * HD + s_c;
             const float4 k0 = *reinterpret_cast<const float4 *>(kp), k1 = *reinterpret_cast<const float4 *>(kp + 4);
             const float4 v0 = *reinterpret_cast<const float4 *>(vp), v1 = *reinterpret_cast<const float4 *>(vp + 4);
@@ -1247,23 +1133,35 @@ __global__ void __launch_bounds__(256) attention_f32_kernel(const AttnArgsF32 a)
     if (a.lse && g == 0 && qvalid) a.lse[(b * a.q_batch_rows + qi) * a.H + h] = l_run > 0.f ? m_run + log2f(l_run) : -INFINITY;
 }
 
-extern "C" int vs_attention_lse(const void *q, const void *k, const void *v, void *out, int32_t nbatch, int32_t H, int32_t Lq,
-                                int32_t Lk, int64_t q_batch_rows, int64_t k_batch_rows, int32_t ldq, int32_t ldk, int32_t ldv,
-                                int32_t ldo, const int32_t *kv_seg, const int32_t *q_kvlen, float scale, int32_t dtype, float *lse,
-                                vs_stream_t stream_);
-
-extern "C" int vs_attention(const void *q, const void *k, const void *v, void *out, int32_t nbatch, int32_t H, int32_t Lq,
-                            int32_t Lk, int64_t q_batch_rows, int64_t k_batch_rows, int32_t ldq, int32_t ldk, int32_t ldv,
-                            int32_t ldo, const int32_t *kv_seg, const int32_t *q_kvlen, float scale, int32_t dtype,
-                            vs_stream_t stream_) {
-    return vs_attention_lse(q, k, v, out, nbatch, H, Lq, Lk, q_batch_rows, k_batch_rows, ldq, ldk, ldv, ldo, kv_seg, q_kvlen, scale, dtype,
-                            nullptr, stream_);
+// the fields every forward kernel reads, from the entry's parameters
+template <class T>
+AttnArgs<T> fill_args(const void *q, const void *k, const void *v, void *out, int nbatch, int H, int Lq, int Lk, int64_t q_batch_rows,
+                      int64_t k_batch_rows, int ldq, int ldk, int ldv, int ldo, const int32_t *kv_seg, const int32_t *q_kvlen, float scale, float *lse,
+                      int out_packed) {
+    AttnArgs<T> a;
+    a.q = (const T *)q; a.k = (const T *)k; a.v = (const T *)v; a.out = (T *)out; a.kv_seg = kv_seg; a.q_kvlen = q_kvlen;
+    a.nbatch = nbatch; a.H = H; a.Lq = Lq; a.Lk = Lk; a.q_batch_rows = q_batch_rows; a.k_batch_rows = k_batch_rows;
+    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.scale_log2e = scale * 1.4426950408889634f; a.lse = lse; a.out_packed = out_packed;
+    return a;
 }
+
+// the packed kernel's block from the common one: the same fields by name, the row strides in bytes (4-byte units in), the tile count
+AttnArgsSP sp_args(const AttnArgsF &a) {
+    AttnArgsSP f;
+    f.q = (const unsigned char *)a.q; f.k = (const unsigned char *)a.k; f.v = (const unsigned char *)a.v; f.out = a.out;
+    f.kv_seg = a.kv_seg; f.q_kvlen = a.q_kvlen; f.nbatch = a.nbatch; f.H = a.H; f.Lq = a.Lq; f.Lk = a.Lk; f.nqt = vs::cdiv(a.Lq, 96);
+    f.q_batch_rows = a.q_batch_rows; f.k_batch_rows = a.k_batch_rows; f.ldq_b = 4LL * a.ldq; f.ldk_b = 4LL * a.ldk; f.ldv_b = 4LL * a.ldv;
+    f.ldo = a.ldo; f.scale_log2e = a.scale_log2e; f.lse = a.lse; f.out_packed = a.out_packed;
+    return f;
+}
+
+}  // namespace
 
 extern "C" int vs_attention_lse(const void *q, const void *k, const void *v, void *out, int32_t nbatch, int32_t H, int32_t Lq,
                                 int32_t Lk, int64_t q_batch_rows, int64_t k_batch_rows, int32_t ldq, int32_t ldk, int32_t ldv,
                                 int32_t ldo, const int32_t *kv_seg, const int32_t *q_kvlen, float scale, int32_t dtype, float *lse,
                                 vs_stream_t stream_) {
+    using vs::route::AttnKind;
     hipStream_t stream = (hipStream_t)stream_;
     VS_CHECK(q && k && v && out, "vs_attention: null pointer");
     VS_CHECK(nbatch >= 0 && H > 0 && Lq >= 0, "vs_attention: bad sizes");
@@ -1280,76 +1178,52 @@ extern "C" int vs_attention_lse(const void *q, const void *k, const void *v, voi
     if (nbatch == 0 || Lq == 0) return 0;
     if (dtype == 4) {
         VS_CHECK(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0 && ((uintptr_t)out & 15) == 0, "vs_attention: split operands need 16-byte aligned f32 rows");
-        if (in_packed) {
-            VS_CHECK(ldq % 32 == 0 && ldk % 32 == 0 && ldv % 32 == 0 && (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 127) == 0,
-                     "vs_attention: packed q | k | v need row strides that are multiples of 32 (4-byte units) and 128-byte aligned head-0 columns");
-            AttnArgsSP f;
-            f.q = (const unsigned char *)q; f.k = (const unsigned char *)k; f.v = (const unsigned char *)v; f.out = (float *)out; f.kv_seg = kv_seg; f.q_kvlen = q_kvlen;
-            f.nbatch = nbatch; f.H = H; f.Lq = Lq; f.Lk = Lk; f.nqt = vs::cdiv(Lq, 32 * 3); f.q_batch_rows = q_batch_rows; f.k_batch_rows = k_batch_rows;
-            f.ldq_b = 4LL * ldq; f.ldk_b = 4LL * ldk; f.ldv_b = 4LL * ldv; f.ldo = ldo; f.scale_log2e = scale * 1.4426950408889634f; f.lse = lse;
-            f.out_packed = out_packed;
-            const long long nwg = (long long)f.nqt * H * nbatch;
-            VS_CHECK(nwg < (1LL << 31), "vs_attention: grid too large");
-            hipLaunchKernelGGL(attention_sp_kernel<3>, dim3((unsigned)nwg), dim3(256), 0, stream, f);
-            VS_HIP(hipGetLastError());
-            return 0;
+        VS_CHECK(!in_packed || (ldq % 32 == 0 && ldk % 32 == 0 && ldv % 32 == 0 && (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 127) == 0),
+                 "vs_attention: packed q | k | v need row strides that are multiples of 32 (4-byte units) and 128-byte aligned head-0 columns");
+    }
+    const vs::route::AttnRoute r = vs::route::attention_route(dtype, in_packed != 0, nbatch, H, Lq, Lk, kv_seg != nullptr, q_kvlen != nullptr);
+    VS_CHECK(r.gx < (1LL << 31), "vs_attention: grid too large");
+    const dim3 grid((unsigned)r.gx, r.gy, r.gz), block(r.block);
+    if (dtype >= 3) {
+        const AttnArgsF a = fill_args<float>(q, k, v, out, nbatch, H, Lq, Lk, q_batch_rows, k_batch_rows, ldq, ldk, ldv, ldo, kv_seg, q_kvlen, scale, lse, out_packed);
+        switch (r.kind) {
+            case AttnKind::Packed96: hipLaunchKernelGGL(attention_sp_kernel<3>, grid, block, 0, stream, sp_args(a)); break;
+            case AttnKind::Split128: hipLaunchKernelGGL((attention_split_kernel<2>), grid, block, 0, stream, a); break;
+            case AttnKind::Split64: hipLaunchKernelGGL((attention_split_kernel<1>), grid, block, 0, stream, a); break;
+            case AttnKind::F32: hipLaunchKernelGGL(attention_f32_kernel, grid, block, 0, stream, a); break;
+            default: VS_CHECK(false, "vs_attention: no 16-bit route for f32 operands");
         }
-        AttnArgsSplit f;
-        f.q = (const float *)q; f.k = (const float *)k; f.v = (const float *)v; f.out = (float *)out; f.kv_seg = kv_seg; f.q_kvlen = q_kvlen;
-        f.nbatch = nbatch; f.H = H; f.Lq = Lq; f.Lk = Lk; f.q_batch_rows = q_batch_rows; f.k_batch_rows = k_batch_rows;
-        f.ldq = ldq; f.ldk = ldk; f.ldv = ldv; f.ldo = ldo; f.scale_log2e = scale * 1.4426950408889634f; f.lse = lse; f.out_packed = out_packed;
-        const int Lk_eff = kv_seg ? 2 * Lk : Lk;
-        const bool big = (long long)vs::cdiv(Lq, 128) * H * nbatch >= 512 && Lk_eff > 256;
-        if (big) hipLaunchKernelGGL((attention_split_kernel<2>), dim3(vs::cdiv(Lq, 128), H, nbatch), dim3(256), 0, stream, f);
-        else hipLaunchKernelGGL((attention_split_kernel<1>), dim3(vs::cdiv(Lq, 64), H, nbatch), dim3(256), 0, stream, f);
-        VS_HIP(hipGetLastError());
-        return 0;
-    }
-    if (dtype == 3) {
-        AttnArgsF32 f;
-        f.q = (const float *)q; f.k = (const float *)k; f.v = (const float *)v; f.out = (float *)out; f.kv_seg = kv_seg; f.q_kvlen = q_kvlen;
-        f.nbatch = nbatch; f.H = H; f.Lq = Lq; f.Lk = Lk; f.q_batch_rows = q_batch_rows; f.k_batch_rows = k_batch_rows;
-        f.ldq = ldq; f.ldk = ldk; f.ldv = ldv; f.ldo = ldo; f.scale_log2e = scale * 1.4426950408889634f; f.lse = lse;
-        hipLaunchKernelGGL(attention_f32_kernel, dim3(vs::cdiv(Lq, 64), H, nbatch), dim3(256), 0, stream, f);
-        VS_HIP(hipGetLastError());
-        return 0;
-    }
-    AttnArgs a;
-    a.q = (const unsigned short *)q; a.k = (const unsigned short *)k; a.v = (const unsigned short *)v;
-    a.out = (unsigned short *)out; a.kv_seg = kv_seg; a.q_kvlen = q_kvlen;
-    a.nbatch = nbatch; a.H = H; a.Lq = Lq; a.Lk = Lk; a.q_batch_rows = q_batch_rows; a.k_batch_rows = k_batch_rows;
-    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
-    a.scale_log2e = scale * 1.4426950408889634f;
-    a.lse = lse;
-    // 128 queries per workgroup when that still leaves >= 2 workgroups per CU; else 64
-    if (!kv_seg && !q_kvlen && Lk <= kResMaxKeys && Lq <= 3 * 8 * 16) {
-        const int Lkp = (Lk + 15) & ~15;
-        const size_t lds = (size_t)(2 * Lkp * KROW) * sizeof(unsigned short);   // K and V, row-major
-        dim3 grid(1, H, nbatch);
-        if (dtype == 2) {
-            VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&attention_res_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL((attention_res_kernel<true>), grid, dim3(512), lds, stream, a);
-        } else {
-            VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&attention_res_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL((attention_res_kernel<false>), grid, dim3(512), lds, stream, a);
+    } else {
+        const AttnArgs16 a = fill_args<unsigned short>(q, k, v, out, nbatch, H, Lq, Lk, q_batch_rows, k_batch_rows, ldq, ldk, ldv, ldo, kv_seg, q_kvlen, scale, lse, 0);
+        switch (r.kind) {
+            case AttnKind::Res: {
+                const int Lkp = (Lk + 15) & ~15;
+                const size_t lds = (size_t)(2 * Lkp * KROW) * sizeof(unsigned short);   // K and V, row-major
+                const void *fn = dtype == 2 ? reinterpret_cast<const void *>(&attention_res_kernel<true>) : reinterpret_cast<const void *>(&attention_res_kernel<false>);
+                VS_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                if (dtype == 2) hipLaunchKernelGGL((attention_res_kernel<true>), grid, block, lds, stream, a);
+                else hipLaunchKernelGGL((attention_res_kernel<false>), grid, block, lds, stream, a);
+                break;
+            }
+            case AttnKind::Tile128:
+                if (dtype == 2) hipLaunchKernelGGL((attention_kernel<true, 2>), grid, block, 0, stream, a);
+                else hipLaunchKernelGGL((attention_kernel<false, 2>), grid, block, 0, stream, a);
+                break;
+            case AttnKind::Tile64:
+                if (dtype == 2) hipLaunchKernelGGL((attention_kernel<true, 1>), grid, block, 0, stream, a);
+                else hipLaunchKernelGGL((attention_kernel<false, 1>), grid, block, 0, stream, a);
+                break;
+            default: VS_CHECK(false, "vs_attention: no f32 route for 16-bit operands");
         }
-        VS_HIP(hipGetLastError());
-        return 0;
     }
-    // 128 queries per workgroup only for long key sequences (more MFMAs per staged tile); the 257/516-key shapes are
-    // latency bound and run faster with 64-query workgroups at higher occupancy
-    const int Lk_eff = kv_seg ? 2 * Lk : Lk;
-    const bool big = (long long)vs::cdiv(Lq, 128) * H * nbatch >= 512 && Lk_eff > 1024;
-    dim3 block(256);
-#define VS_LAUNCH(QG_)                                                                                         \
-    {                                                                                                          \
-        dim3 grid(vs::cdiv(Lq, 64 * QG_), H, nbatch);                                                          \
-        if (dtype == 2) hipLaunchKernelGGL((attention_kernel<true, QG_>), grid, block, 0, stream, a);          \
-        else hipLaunchKernelGGL((attention_kernel<false, QG_>), grid, block, 0, stream, a);                    \
-    }
-    if (big) VS_LAUNCH(2)
-    else VS_LAUNCH(1)
-#undef VS_LAUNCH
     VS_HIP(hipGetLastError());
     return 0;
+}
+
+extern "C" int vs_attention(const void *q, const void *k, const void *v, void *out, int32_t nbatch, int32_t H, int32_t Lq,
+                            int32_t Lk, int64_t q_batch_rows, int64_t k_batch_rows, int32_t ldq, int32_t ldk, int32_t ldv,
+                            int32_t ldo, const int32_t *kv_seg, const int32_t *q_kvlen, float scale, int32_t dtype,
+                            vs_stream_t stream_) {
+    return vs_attention_lse(q, k, v, out, nbatch, H, Lq, Lk, q_batch_rows, k_batch_rows, ldq, ldk, ldv, ldo, kv_seg, q_kvlen, scale, dtype,
+                            nullptr, stream_);
 }

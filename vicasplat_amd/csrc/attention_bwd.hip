@@ -11,20 +11,11 @@
 //                                                               because with key segments a K/V row serves several batch items;
 //                                                               without segments 16-bit stores in place (vs_attention_backward16)
 // S and dP are recomputed in both kernels (7 instead of 5 MFMA products per (i, j) tile, no atomics on dQ).
-#include "common.h"
+#include "attention_common.h"
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-constexpr int HD = 64, TB = 64;
-// LDS transpose read (ds_read_b64_tr_b16, tools/probe/tr_read.hip): lane t of a 16-lane group supplies the address of 4 consecutive
-// halfs of row (row0 + (t >> 2)) at column col0 + (t & 3) * 4 and receives tile[row0 .. row0 + 3][col0 + t].  With it the "k along
-// rows" MFMA operands (dO^T, Q^T, K^T) are gathered from the ROW-MAJOR tiles: no transposed LDS images, no packing pass (tr_rows4_sw
-// below, on the swizzled 128-byte rows the LDS-DMA staging writes).
-typedef short tr4_t __attribute__((ext_vector_type(4)));
+constexpr int TB = 64;
 
 struct AttnBwdArgs {
     const unsigned short *q, *k, *v, *o, *dout;
@@ -46,49 +37,20 @@ struct AttnBwdArgs {
     int ldo32, lddo32, lddq32, kv_direct;
 };
 
-// (tile, head, batch) of this workgroup.  The hardware deals consecutive workgroups (x fastest) to consecutive XCDs, which puts the tiles of one
-// (batch, head) -- they all read that head's whole K / V (dq kernels) or Q / dO (dk|dv kernels) -- behind eight different L2s (counters: 76 GB
-// fetched per 8-scene split training step for ~38 GB of operands).  So consecutive LOGICAL ids share an XCD (gemm256_kernel's remap).
+// (tile, head, batch) of this workgroup of a 3-D grid.  The hardware deals consecutive workgroups (x fastest) to consecutive XCDs, which puts the
+// tiles of one (batch, head) -- they all read that head's whole K / V (dq kernels) or Q / dO (dk|dv kernels) -- behind eight different
+// L2s (counters: 76 GB fetched per 8-scene split training step for ~38 GB of operands).  So consecutive LOGICAL ids share an XCD: linear id ->
+// xcd_remap (routes.h) -> unflatten.
 __device__ __forceinline__ void block_bhx(int &b, int &h, int &x) {
     const int gx = gridDim.x, gy = gridDim.y, n = gx * gy * gridDim.z;
-    const int lin = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-    const int q = n >> 3, r = n & 7, xc = lin & 7, idx = lin >> 3;
-    const int l = (xc < r ? xc * (q + 1) : r * (q + 1) + (xc - r) * q) + idx;
+    const int l = vs::route::xcd_remap(blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z), n);
     x = l % gx; const int t = l / gx; h = t % gy; b = t / gy;
 }
 
 template <bool BF16>
-__device__ __forceinline__ f4 mfma(const uint4 &a, const uint4 &b, f4 c) {
-    if constexpr (BF16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf8 *>(&a), *reinterpret_cast<const bf8 *>(&b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const half8 *>(&a), *reinterpret_cast<const half8 *>(&b), c, 0, 0, 0);
-}
-template <bool BF16>
 __device__ __forceinline__ float ld16(unsigned short h) {
     if constexpr (BF16) return __uint_as_float(((unsigned)h) << 16);
     else return (float)*reinterpret_cast<_Float16 *>(&h);
-}
-template <bool BF16>
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-    // one packed convert (round to nearest even) instead of two converts + an OR: the softmax / dS path is VALU-bound
-    unsigned r;
-    if constexpr (BF16) asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    else asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// The same convert for a value that goes straight into an MFMA: compiler-visible instructions, so that the hazard recogniser inserts the
-// VALU-write -> MFMA-read wait states (it does not look inside inline asm; attention.hip, pack2v).
-template <bool BF16>
-__device__ __forceinline__ unsigned pack2v(float a, float b) {
-    typedef float f2p_ __attribute__((ext_vector_type(2)));
-    if constexpr (BF16) {
-        typedef __bf16 b2p_ __attribute__((ext_vector_type(2)));
-        return __builtin_bit_cast(unsigned, __builtin_convertvector(f2p_{a, b}, b2p_));
-    } else {
-        typedef _Float16 h2p_ __attribute__((ext_vector_type(2)));
-        return __builtin_bit_cast(unsigned, __builtin_convertvector(f2p_{a, b}, h2p_));
-    }
 }
 
 // 8 lanes per (row, head): each lane multiplies 8 elements (one 16-byte load of O and of dO), three DPP steps sum the 8 lanes.
@@ -116,25 +78,7 @@ attn_delta_kernel(const AttnBwdArgs a, long long rows) {
     if (live && sub == 0) a.delta[item] = v;
 }
 
-struct KeyList {
-    int base0, len0, base1, len1, Lk;
-    __device__ __forceinline__ long long row(int j) const {
-        j = min(j, Lk - 1);
-        return j < len0 ? (long long)base0 + j : (long long)base1 + (j - len0);
-    }
-};
-__device__ __forceinline__ KeyList key_list(const AttnBwdArgs &a, int b) {
-    KeyList kl;
-    if (a.kv_seg) {
-        kl.base0 = a.kv_seg[4 * b + 0]; kl.len0 = a.kv_seg[4 * b + 1]; kl.base1 = a.kv_seg[4 * b + 2]; kl.len1 = a.kv_seg[4 * b + 3];
-    } else {
-        kl.base0 = (int)(b * a.k_batch_rows); kl.len0 = a.Lk; kl.base1 = 0; kl.len1 = 0;
-    }
-    kl.Lk = kl.len0 + kl.len1;
-    return kl;
-}
-
-// ---- asynchronous staging (round 2): the 64 x 64 tiles are filled by LDS-DMA (global_load_lds_dwordx4: no staging registers, so
+// ---- asynchronous staging (round 2): the 64 x 64 tiles are filled by LDS-DMA (glds16: no staging registers, so
 // no occupancy cost -- a register-prefetch variant lost more to occupancy than it won) into a two-slot ring, the NEXT tile in flight
 // while the current one is multiplied, one barrier per tile.  The synchronous version (load -> LDS store -> barrier -> compute ->
 // barrier) spent ~3.3 us per tile and workgroup against ~0.7 us of MFMA + VALU work: latency-bound with 3-4 workgroups per CU.
@@ -143,11 +87,9 @@ __device__ __forceinline__ KeyList key_list(const AttnBwdArgs &a, int b) {
 // 16-byte slots of the 256-byte bank row, and the four rows of a transpose read into different windows.  Rows past the end of the
 // list are duplicates of the last row (a DMA cannot zero-fill): their scores are finite and their probabilities are forced to 0 by
 // the existing masks (L = +inf for missing queries; key >= my_len for missing keys: a tile with a missing key is never "full").
-typedef void __attribute__((address_space(3))) *lds_ptr_t;
-__device__ __forceinline__ void glds16(const void *gp, unsigned lds_off) {   // (inline asm: the compiler adds no waits of its own)
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds_off), "v"(gp) : "memory");
-}
 __device__ __forceinline__ int sw_off(int row, int chunk) { return row * HD + ((chunk ^ ((row >> 1) & 7)) << 3); }   // halfs
+// The "k along rows" MFMA operands (dO^T, Q^T, K^T) are gathered from the ROW-MAJOR tiles by the LDS transpose read (tr4_t): no transposed LDS
+// images, no packing pass -- here on the swizzled 128-byte rows that the LDS-DMA staging writes.
 __device__ __forceinline__ uint2 tr_rows4_sw(const unsigned short *tile, int row0, int col0, int t) {
     typedef tr4_t __attribute__((address_space(3))) *trp_t;
     const int row = row0 + (t >> 2), col = col0 + (t & 3) * 4;
@@ -193,7 +135,7 @@ attn_bwd_dq_kernel(const AttnBwdArgs a) {
         qvalid[u] = qi < a.Lq;
         if (q0 + (u * 4 + wid) * 16 < a.Lq) nact = u + 1;          // (wave-uniform: groups 0 .. nact - 1 hold at least one real query)
         qrow[u] = b * a.q_batch_rows + (qvalid[u] ? qi : a.Lq - 1);
-        my_len[u] = qvalid[u] ? kl.Lk : 0;
+        my_len[u] = qvalid[u] ? kl.Lk : 0;          // (query_len, in the form this kernel was compiled from: the other form moves its loop body)
         if (a.q_kvlen && qvalid[u]) my_len[u] = min(kl.Lk, a.q_kvlen[(long long)b * a.Lq + qi]);
         // B-operand fragments (rows = queries): Q and dO
         const unsigned short *qp = a.q + qrow[u] * a.ldq + h * HD + g * 8, *dop = a.dout + qrow[u] * a.lddo + h * HD + g * 8;
@@ -348,7 +290,7 @@ attn_bwd_dkv_kernel(const AttnBwdArgs a) {
         const long long row = b * a.q_batch_rows + (ok ? qi : a.Lq - 1);
         aL = ok ? a.lse[row * a.H + h] : INFINITY;
         aD = ok ? a.delta[row * a.H + h] : 0.f;
-        aN = !ok ? 0 : (a.q_kvlen ? min(kl.Lk, a.q_kvlen[(long long)b * a.Lq + qi]) : kl.Lk);
+        aN = !ok ? 0 : (a.q_kvlen ? min(kl.Lk, a.q_kvlen[(long long)b * a.Lq + qi]) : kl.Lk);     // (query_len; see attn_bwd_dq_kernel)
     };
     auto aux_store = [&](int slot) {   // (tid < 64 is exactly wave 0)
         sL2[slot][tid] = aL; sD2[slot][tid] = aD; sLen2[slot][tid] = aN;
@@ -546,7 +488,7 @@ attn_bwd_dq_split_kernel(const AttnBwdArgs a) {
         qvalid[u] = qi < a.Lq;
         if (q0 + (u * 4 + wid) * 16 < a.Lq) nact = u + 1;
         qrow[u] = b * a.q_batch_rows + (qvalid[u] ? qi : a.Lq - 1);
-        my_len[u] = qvalid[u] ? kl.Lk : 0;
+        my_len[u] = qvalid[u] ? kl.Lk : 0;          // (query_len, in the form this kernel was compiled from: the other form moves its loop body)
         if (a.q_kvlen && qvalid[u]) my_len[u] = min(kl.Lk, a.q_kvlen[(long long)b * a.Lq + qi]);
         const long long qo = qrow[u] * a.ldq + h * HD + g * 8, dO = qrow[u] * a.lddo + h * HD + g * 8;
         qh[u][0] = *reinterpret_cast<const uint4 *>(a.q + qo); qh[u][1] = *reinterpret_cast<const uint4 *>(a.q + qo + 32);
@@ -681,7 +623,7 @@ attn_bwd_dkv_split_kernel(const AttnBwdArgs a) {
         const long long row = b * a.q_batch_rows + (ok ? qi : a.Lq - 1);
         aL = ok ? a.lse[row * a.H + h] : INFINITY;
         aD = ok ? a.delta[row * a.H + h] : 0.f;
-        aN = !ok ? 0 : (a.q_kvlen ? min(kl.Lk, a.q_kvlen[(long long)b * a.Lq + qi]) : kl.Lk);
+        aN = !ok ? 0 : (a.q_kvlen ? min(kl.Lk, a.q_kvlen[(long long)b * a.Lq + qi]) : kl.Lk);     // (query_len; see attn_bwd_dq_kernel)
     };
     auto aux_store = [&](int slot) { sL2[slot][tid] = aL; sD2[slot][tid] = aD; sLen2[slot][tid] = aN; };
     if (a.Lq > 0) {
@@ -785,9 +727,19 @@ attn_bwd_dkv_split_kernel(const AttnBwdArgs a) {
     }
 }
 
-}  // namespace
+// the fields both operand classes share, from the entries' parameters (q .. dout: the 16-bit tensors, or the hi images of the split class)
+AttnBwdArgs fill_bwd_args(const void *q, const void *k, const void *v, const void *dout, const float *lse, float *delta, float *dk, float *dv, int nbatch,
+                          int H, int Lq, int Lk, int64_t q_batch_rows, int64_t k_batch_rows, int ldq, int ldk, int ldv, int lddo, int lddk, int lddv,
+                          const int32_t *kv_seg, const int32_t *q_kvlen, float scale) {
+    AttnBwdArgs a = {};
+    a.q = (const unsigned short *)q; a.k = (const unsigned short *)k; a.v = (const unsigned short *)v; a.dout = (const unsigned short *)dout;
+    a.lse = lse; a.delta = delta; a.dk = dk; a.dv = dv; a.kv_seg = kv_seg; a.q_kvlen = q_kvlen;
+    a.nbatch = nbatch; a.H = H; a.Lq = Lq; a.Lk = Lk; a.q_batch_rows = q_batch_rows; a.k_batch_rows = k_batch_rows;
+    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.lddo = lddo; a.lddk = lddk; a.lddv = lddv;
+    a.scale = scale; a.scale_log2e = scale * 1.4426950408889634f;
+    return a;
+}
 
-namespace {
 int attention_backward_impl(const void *q, const void *k, const void *v, const void *o, const void *dout, const float *lse,
                             float *delta, void *dq, float *dk, float *dv, void *dk16, void *dv16, int32_t nbatch, int32_t H, int32_t Lq, int32_t Lk,
                             int64_t q_batch_rows, int64_t k_batch_rows, int32_t ldq, int32_t ldk, int32_t ldv, int32_t ldo,
@@ -802,17 +754,12 @@ int attention_backward_impl(const void *q, const void *k, const void *v, const v
     VS_CHECK((((uintptr_t)o | (uintptr_t)dout) & 15) == 0, "vs_attention_backward: o and dout must be 16-byte aligned");
     VS_CHECK(kv_seg ? max_keys > 0 : Lk > 0, "vs_attention_backward: Lk (or max_keys with kv_seg) must be positive");
     if (nbatch == 0 || Lq == 0) return 0;
-    AttnBwdArgs a;
-    a.q = (const unsigned short *)q; a.k = (const unsigned short *)k; a.v = (const unsigned short *)v;
-    a.o = (const unsigned short *)o; a.dout = (const unsigned short *)dout; a.lse = lse; a.delta = delta;
-    a.dq = (unsigned short *)dq; a.dk = dk; a.dv = dv; a.dk16 = (unsigned short *)dk16; a.dv16 = (unsigned short *)dv16; a.kv_seg = kv_seg; a.q_kvlen = q_kvlen;
-    a.nbatch = nbatch; a.H = H; a.Lq = Lq; a.Lk = Lk; a.q_batch_rows = q_batch_rows; a.k_batch_rows = k_batch_rows;
-    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.lddo = lddo; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
-    a.scale = scale; a.scale_log2e = scale * 1.4426950408889634f;
+    AttnBwdArgs a = fill_bwd_args(q, k, v, dout, lse, delta, dk, dv, nbatch, H, Lq, Lk, q_batch_rows, k_batch_rows, ldq, ldk, ldv, lddo, lddk, lddv, kv_seg, q_kvlen, scale);
+    a.o = (const unsigned short *)o; a.dq = (unsigned short *)dq; a.dk16 = (unsigned short *)dk16; a.dv16 = (unsigned short *)dv16; a.ldo = ldo; a.lddq = lddq;
     const long long rows = (long long)(nbatch - 1) * q_batch_rows + Lq;
-    const int keys = kv_seg ? max_keys : Lk;
+    const vs::route::AttnBwdRoute r = vs::route::attention_bwd_route(false, Lq, Lk, kv_seg != nullptr, max_keys);
     dim3 block(256);
-    const dim3 gq(vs::cdiv(Lq, 128), H, nbatch), gk(vs::cdiv(keys, 128), H, nbatch);   // two row groups of 16 per wave
+    const dim3 gq(r.gq, H, nbatch), gk(r.gk, H, nbatch);
     if (dtype == 2) {
         hipLaunchKernelGGL(attn_delta_kernel<true>, dim3((unsigned)vs::cdiv64(rows * H, 32)), block, 0, stream, a, rows);
         hipLaunchKernelGGL((attn_bwd_dq_kernel<true, 2>), gq, block, 0, stream, a);
@@ -866,23 +813,17 @@ extern "C" int vs_attention_backward_split(const void *q_hi, const void *q_lo, c
                (uintptr_t)do_lo | (uintptr_t)o | (uintptr_t)dout | (uintptr_t)dq) & 15) == 0, "vs_attention_backward_split: 16-byte alignment required");
     VS_CHECK(kv_seg ? max_keys > 0 : Lk > 0, "vs_attention_backward_split: Lk (or max_keys with kv_seg) must be positive");
     if (nbatch == 0 || Lq == 0) return 0;
-    AttnBwdArgs a;
-    a.q = (const unsigned short *)q_hi; a.k = (const unsigned short *)k_hi; a.v = (const unsigned short *)v_hi; a.dout = (const unsigned short *)do_hi;
+    AttnBwdArgs a = fill_bwd_args(q_hi, k_hi, v_hi, do_hi, lse, delta, dk, dv, nbatch, H, Lq, Lk, q_batch_rows, k_batch_rows, ldq, ldk, ldv, lddo, lddk, lddv, kv_seg, q_kvlen, scale);
     a.q_lo = (const unsigned short *)q_lo; a.k_lo = (const unsigned short *)k_lo; a.v_lo = (const unsigned short *)v_lo; a.dout_lo = (const unsigned short *)do_lo;
-    a.o = nullptr; a.o32 = o; a.dout32 = dout; a.lse = lse; a.delta = delta;
-    a.dq = nullptr; a.dq32 = dq; a.dk = dk; a.dv = dv; a.dk16 = nullptr; a.dv16 = nullptr; a.kv_seg = kv_seg; a.q_kvlen = q_kvlen;
-    a.nbatch = nbatch; a.H = H; a.Lq = Lq; a.Lk = Lk; a.q_batch_rows = q_batch_rows; a.k_batch_rows = k_batch_rows;
-    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = 0; a.lddo = lddo; a.lddq = 0; a.lddk = lddk; a.lddv = lddv;
-    a.ldo32 = ldo32; a.lddo32 = lddo32; a.lddq32 = lddq; a.kv_direct = kv_seg ? 0 : 1;
-    a.scale = scale; a.scale_log2e = scale * 1.4426950408889634f;
+    a.o32 = o; a.dout32 = dout; a.dq32 = dq; a.ldo32 = ldo32; a.lddo32 = lddo32; a.lddq32 = lddq; a.kv_direct = kv_seg ? 0 : 1;
     const long long rows = (long long)(nbatch - 1) * q_batch_rows + Lq;
-    const int keys = kv_seg ? max_keys : Lk;
+    const vs::route::AttnBwdRoute r = vs::route::attention_bwd_route(true, Lq, Lk, kv_seg != nullptr, max_keys);
     dim3 block(256);
     hipLaunchKernelGGL(attn_delta_f32_kernel, dim3((unsigned)vs::cdiv64(rows * H, 32)), block, 0, stream, a, rows);
     // dQ: two row groups of 16 per wave.  dK / dV: one -- two key groups need 64 + 64 + 64 registers for the K | V fragments, the accumulators
     // and the (hi, lo) P | dS fragments alone: the NG = 2 instantiation spilled 102 VGPRs under the 256-register cap
-    hipLaunchKernelGGL(attn_bwd_dq_split_kernel<2>, dim3(vs::cdiv(Lq, 128), H, nbatch), block, 0, stream, a);
-    hipLaunchKernelGGL(attn_bwd_dkv_split_kernel<1>, dim3(vs::cdiv(keys, 64), H, nbatch), block, 0, stream, a);
+    hipLaunchKernelGGL(attn_bwd_dq_split_kernel<2>, dim3(r.gq, H, nbatch), block, 0, stream, a);
+    hipLaunchKernelGGL(attn_bwd_dkv_split_kernel<1>, dim3(r.gk, H, nbatch), block, 0, stream, a);
     VS_HIP(hipGetLastError());
     return 0;
 }

@@ -473,11 +473,7 @@ __global__ void __launch_bounds__(512, 1) conv3x3_256_kernel(const ConvArgs g, c
     const int tiles_n = (g.Cout + 255) / 256;
     const int tiles_m = (M + 255) / 256;
     const int nwg = tiles_m * tiles_n;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, idx = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = vs::route::xcd_remap(blockIdx.x, nwg);
     const int tm = bid / tiles_n, tn = bid % tiles_n;
     const int m0 = tm * 256, n0 = tn * 256;
 
@@ -550,11 +546,7 @@ __global__ void __launch_bounds__(512, 1) conv3x3_256_halo_split_kernel(const Co
     const int K = 9 * g.Cin;
     const int tiles_x = g.W >> 4, tiles_img = (g.H >> 4) * tiles_x;
     const int nwg = g.Nimg * tiles_img;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, idx = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = vs::route::xcd_remap(blockIdx.x, nwg);
     const int nimg = bid / tiles_img, trem = bid - nimg * tiles_img;
     const int y0 = (trem / tiles_x) * 16, x0 = (trem % tiles_x) * 16;
 
@@ -629,11 +621,7 @@ __global__ void __launch_bounds__(512, 1) conv3x3_256x128_split_kernel(const Con
     const int K = 9 * g.Cin;
     const int tiles_n = (g.Cout + 127) / 128;
     const int nwg = ((M + 255) / 256) * tiles_n;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, idx = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = vs::route::xcd_remap(blockIdx.x, nwg);
     const int tm = bid / tiles_n, tn = bid % tiles_n;
     const int m0 = tm * 256, n0 = tn * 128;
     ConvStager256x128 st;
@@ -755,11 +743,7 @@ __global__ void __launch_bounds__(256, (MI == 8 || BF16 == kDtSplit) ? 2 : 3) co
     const int tiles_n = (g.Cout + BN - 1) / BN;
     const int tiles_m = (M + BM - 1) / BM;
     const int nwg = tiles_m * tiles_n;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, idx = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = vs::route::xcd_remap(blockIdx.x, nwg);
     // n-fastest tile order: the (few) Cout tiles of one pixel tile run back to back and share the A panel in L2
     const int tm = bid / tiles_n, tn = bid % tiles_n;
     const int m0 = tm * BM, n0 = tn * BN;

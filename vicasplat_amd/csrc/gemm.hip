@@ -75,8 +75,7 @@ __global__ void __launch_bounds__(256, (MI == 8 || BF16 == kDtSplit) ? 2 : 3) ge
     if (lin_tile >= 0) {
         bid = lin_tile;
     } else {
-        const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, idx = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+        bid = vs::route::xcd_remap(bid, nwg);
     }
     const int tm = bid / tiles_n, tn = bid % tiles_n;
     const int m0 = g.m_lo + tm * BM, n0 = tn * BN;
@@ -567,11 +566,7 @@ __global__ void __launch_bounds__(512, 1) conv7x7_256_kernel(const GemmArgs g) {
     const int wr = wid >> 2, wc = wid & 3;
     const int tiles_n = (g.N + BN2 - 1) / BN2;
     const int nwg = ((g.M + BM2 - 1) / BM2) * tiles_n;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, idx = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = vs::route::xcd_remap(blockIdx.x, nwg);
     const int tm = bid / tiles_n, tn = bid % tiles_n;
     const int m0 = tm * BM2, n0 = tn * BN2;
     const unsigned short *A = reinterpret_cast<const unsigned short *>(g.A);

@@ -19,6 +19,7 @@
 // ds_read only by the issuer's vmcnt wait followed by a barrier both have passed.
 #pragma once
 #include "gemm_common.h"
+#include "routes.h"
 
 namespace {
 
@@ -669,11 +670,7 @@ __global__ void __launch_bounds__(512, 1) gemm256_kernel(const GemmArgs g) {
     const int tiles_n = (g.N + BN2 - 1) / BN2;
     const int tiles_m = (g.M - g.m_lo + BM2 - 1) / BM2;
     const int nwg = tiles_m * tiles_n;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, idx = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = vs::route::xcd_remap(blockIdx.x, nwg);
     const int tm = bid / tiles_n, tn = bid % tiles_n;
     const int m0 = g.m_lo + tm * BM2, n0 = tn * BN2;
 
@@ -705,9 +702,7 @@ __global__ void __launch_bounds__(512, 1) gemm256_kernel(const GemmArgs g) {
 // ~55 GB of operands, at 4-5.5 TB/s.  Consecutive LOGICAL ids share an XCD (gemm256_kernel's remap): the nine taps / the tiles of one K slice
 // meet in one L2.
 __device__ __forceinline__ int splitk_logical_block() {
-    const int b = blockIdx.x;
-    const int n = gridDim.x, q = n >> 3, r = n & 7, xcd = b & 7, idx = b >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    return vs::route::xcd_remap(blockIdx.x, gridDim.x);
 }
 
 // Split-K / tap-fused variant for weight gradients: out32[tap][M,N] += A[M, Kslice] (W + shift[tap])[N, Kslice]^T through f32

@@ -1,14 +1,31 @@
-// Which kernels a forward GEMM / 3x3 convolution call reaches: pure functions of integers and booleans, no HIP.  gemm.hip and conv.hip
-// launch what these return; tests/test_routes_cpu.py compiles them on the host (tests/route_probe.cpp) and compares them with
-// tests/gemm_f64.py plan(), the pinned shapes of the convolution routes and the thresholds model/encoder/heads/dpt.py repeats.
+// Which kernels a forward GEMM / 3x3 convolution / attention call reaches: pure functions of integers and booleans, no HIP.  gemm.hip,
+// conv.hip, attention.hip and attention_bwd.hip launch what these return; tests/test_routes_cpu.py compiles them on the host
+// (tests/route_probe.cpp) and compares them with tests/gemm_f64.py plan(), the pinned shapes of the convolution and attention routes, the
+// route every case of tests/attention_route_cases.py names, and the thresholds model/encoder/heads/dpt.py repeats.
 #pragma once
 #include <cstdint>
+
+// for xcd_remap, the one function here that kernels call too
+#ifdef __HIPCC__
+#define VS_HOST_DEVICE __host__ __device__
+#else
+#define VS_HOST_DEVICE
+#endif
 
 namespace vs {
 namespace route {
 
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline long long cdiv64(long long a, long long b) { return (a + b - 1) / b; }
+
+// XCD-aware workgroup order.  The hardware deals consecutive workgroup ids to consecutive XCDs (8 on
+// MI355X, each with its own L2): ids b, b + 8, b + 16 .. share one.  This maps id `bid` of a grid of n to a LOGICAL id so that each XCD gets one
+// contiguous range of them (the first n % 8 XCDs one more than the rest) and neighbouring logical ids meet in one L2.  A permutation of [0, n)
+// for every n >= 1: tests/test_routes_cpu.py.
+VS_HOST_DEVICE inline int xcd_remap(int bid, int n) {
+    const int q = n / 8, r = n % 8, xcd = bid % 8, idx = bid / 8;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
 
 // ---- forward GEMM.  Classes as the kernels' template argument (gemm_common.h): 0 f16, 1 bf16, 2 f32 MFMA, 3 split; K2 counts 2-byte units. ----
 constexpr int kF32 = 2, kSplit = 3;
@@ -155,6 +172,34 @@ inline ConvRoute conv3x3_route(int dtype, long long M, int H, int W, int Cin2, i
     if (big >= 512) return {ConvKind::Wave4, 0, 8, big};
     if (t4 <= 192 && M > 64) return {ConvKind::Wave4, 0, 2, cdiv64(M, 64) * cdiv(Cout, 128)};
     return {ConvKind::Wave4, 0, 4, t4};
+}
+
+// ---- attention (attention.hip, attention_bwd.hip).  dtype as the ABI after its packing bits are taken off: 1 f16, 2 bf16, 3 f32, 4 split. ----
+// The resident kernel holds all keys of a (batch, head) in LDS (its staging rounds are sized by kResMaxKeys) and walks 3 x 8 groups of 16 queries.
+constexpr int kResMaxKeys = 320, kResMaxQueries = 3 * 8 * 16;
+enum class AttnKind { Res, Tile64, Tile128, F32, Split64, Split128, Packed96 };
+struct AttnRoute { AttnKind kind; long long gx; int gy, gz, block; };    // grid (gx, gy, gz); Packed96's is linear: gx = tiles * H * nbatch
+
+inline AttnRoute attention_route(int dtype, bool in_packed, int nbatch, int H, int Lq, int Lk, bool has_seg, bool has_len) {
+    if (dtype == 4 && in_packed) return {AttnKind::Packed96, (long long)cdiv(Lq, 96) * H * nbatch, 1, 1, 256};
+    if (dtype == 3) return {AttnKind::F32, cdiv(Lq, 64), H, nbatch, 256};
+    if (dtype != 4 && !has_seg && !has_len && Lk <= kResMaxKeys && Lq <= kResMaxQueries) return {AttnKind::Res, 1, H, nbatch, 512};
+    // Lk as the entry receives it.  Every caller of this project passes Lk = 0 with key segments (the lengths are in kv_seg), so Lk_eff is 0
+    // there and a segmented call always takes the 64-query kernels.
+    const int Lk_eff = has_seg ? 2 * Lk : Lk;
+    // 128 queries per workgroup (more MFMAs per staged K / V tile) when that still leaves >= 2 workgroups per CU, and only for long key
+    // lists: the 257 / 516-key shapes are latency bound and run faster with 64-query workgroups at higher occupancy
+    const bool big = (long long)cdiv(Lq, 128) * H * nbatch >= 512 && Lk_eff > (dtype == 4 ? 256 : 1024);
+    const AttnKind kind = dtype == 4 ? (big ? AttnKind::Split128 : AttnKind::Split64) : (big ? AttnKind::Tile128 : AttnKind::Tile64);
+    return {kind, cdiv(Lq, big ? 128 : 64), H, nbatch, 256};
+}
+
+// backward: x-extent of the dq and the dk|dv grids (times H x nbatch); `keys` bounds the key list of every batch item.  16-bit: two 16-row
+// groups per wave in both kernels; split: two for dq, one for dk|dv (two key groups spill, attention_bwd.hip)
+struct AttnBwdRoute { int keys, gq, gk; };
+inline AttnBwdRoute attention_bwd_route(bool split, int Lq, int Lk, bool has_seg, int max_keys) {
+    const int keys = has_seg ? max_keys : Lk;
+    return {keys, cdiv(Lq, 128), cdiv(keys, split ? 64 : 128)};
 }
 
 }  // namespace route
