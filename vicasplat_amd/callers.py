@@ -26,6 +26,9 @@ scripts do around the encoder/decoder:
     csrc/trajectory.hip, batched over scenes, device tensors out
   * `test_step` — ModelWrapper.test_step, src/model/model_wrapper.py:323-381: the six numbers it logs, per scene, batched
   * `pose_eval_step` — PoseEvaluator.test_step, src/evaluation/pose_evaluator.py:77-174: the pose metrics before and after refinement
+  * `validation_step`, `render_video_generic`, `render_video_interpolation_step`, `depth_video_frames` — ModelWrapper.validation_step and
+    render_video_generic / render_video_interpolation (model_wrapper.py:524-704, 710-730, 776-815): metrics, the comparison image, the
+    projections and the uint8 video frames as device tensors, on csrc/viz.hip (depth range, colour maps, frames)
   * `configure_optimizer`, `training_step` — ModelWrapper.configure_optimizers / training_step (model_wrapper.py:884-951,
     184-321): AdamW(lr, wd 0.05, betas 0.9/0.95) with the backbone-lr multiplier, encoder -> rasterizer -> MSE ->
     backward on the HIP kernels (vicasplat_amd.autograd) -> optional gradient all-reduce -> clip 0.5 -> step.
@@ -1145,3 +1148,107 @@ def pose_eval_step(encoder, decoder, batch: dict, *, steps: int = 0, rot_lr: flo
     before = camera_eval_metrics(pred, gt, sample_stride, return_valid=True)
     names = ("ate", "rpe_trans", "rpe_rot", "pose_valid")
     return {**{f"{n}_after_opt": t for n, t in zip(names, after)}, **{f"{n}_before_opt": t for n, t in zip(names, before)}}
+
+
+# ---- validation step: colour maps, comparison image, projections, video (model_wrapper.py:524-704, 776-813) --------------------------------
+def depth_video_frames(color: Tensor, depth: Tensor, gap: int = 8) -> Tensor:
+    """color [F, 3, H, W], depth [F, H, W] -> uint8 [F, 3, 2 H + gap, W]: each frame over its `turbo` depth map (the range taken over all
+    F depth maps, as vis_depth_map(output.depth[0]) takes it), a white gap between them -- render_video_generic's
+    vcat(rgb, depth) ... (video.clip(0, 1) * 255).type(torch.uint8) as one selection and one frame kernel (csrc/viz.hip)."""
+    from . import ops
+    from .visualization.color_map import device_table
+    depth = depth.detach().float().contiguous()
+    return ops.video_frames(color.detach().float().contiguous(), depth, ops.depth_range(depth), device_table("turbo", depth.device), gap)
+
+
+@torch.no_grad()
+def render_video_generic(encoder, decoder, batch: dict, trajectory_fn, num_frames: int = 30, smooth: bool = True, loop_reverse: bool = True,
+                         save_depth: bool = True) -> Tensor:
+    """ModelWrapper.render_video_generic (model_wrapper.py:776-815) up to the frames it hands to wandb: the encoder on batch["context"],
+    `trajectory_fn(t) -> (extrinsics [1, F, 4, 4], intrinsics [1, F, 3, 3])` for t = linspace(0, 1, num_frames) (smooth: eased by
+    (cos(pi (t + 1)) + 1) / 2), the first context view's near and far for every frame, one render with depth, and the frames as uint8
+    [F', 3, Hf, W] ON THE DEVICE: Hf = 2 H + 8 with save_depth (depth_video_frames), else H; loop_reverse appends video[::-1][1:-1].
+    Out of scope: the mp4 / wandb / file output (a caller copies the frames to the host when it wants them)."""
+    ctx = batch["context"]
+    gaussians = encoder(ctx, compute_viewspace_depth=False)["gaussians"]
+    t = torch.linspace(0, 1, num_frames, dtype=torch.float32, device=ctx["extrinsics"].device)
+    if smooth:
+        t = (torch.cos(torch.pi * (t + 1)) + 1) / 2
+    extrinsics, intrinsics = trajectory_fn(t)
+    h, w = ctx["image"].shape[-2:]
+    near, far = ctx["near"][:, :1].expand(-1, num_frames), ctx["far"][:, :1].expand(-1, num_frames)
+    output = decoder.forward(gaussians, extrinsics, intrinsics, near, far, (h, w), "depth")
+    if save_depth:
+        video = depth_video_frames(output.color[0], output.depth[0])
+    else:
+        video = (output.color[0].clip(min=0, max=1) * 255).type(torch.uint8)
+    if loop_reverse:
+        video = torch.cat([video, video.flip(dims=(0,))[1:-1]], dim=0)
+    return video
+
+
+def render_video_interpolation_step(encoder, decoder, batch: dict, **kw) -> Tensor:
+    """ModelWrapper.render_video_interpolation (model_wrapper.py:710-730): render_video_generic along the interpolation between the first
+    and the last context camera of scene 0.  (`render_video_interpolation` above is the demo's multi-view variant and is unchanged.)"""
+    ctx = batch["context"]
+
+    def trajectory_fn(t):
+        return (interpolate_extrinsics(ctx["extrinsics"][:1, 0], ctx["extrinsics"][:1, -1], t),
+                interpolate_intrinsics(ctx["intrinsics"][:1, 0].float(), ctx["intrinsics"][:1, -1].float(), t))
+
+    return render_video_generic(encoder, decoder, batch, trajectory_fn, **kw)
+
+
+@torch.no_grad()
+def validation_step(encoder, decoder, batch: dict, *, lpips_net: LpipsVgg | None = None, distiller=None, distill_only: bool = False,
+                    video: bool = True, projections: bool = True) -> dict:
+    """ModelWrapper.validation_step (model_wrapper.py:524-704) for a batch of one scene, as device tensors: no .item() and no host copy of
+    a result here or in the visualisation functions it calls.  (The decoder's camera set-up, `camera_matrices`, inverts the poses with
+    torch.linalg.inv, which looks at its status on the host: rendering waits for the device there, as it does in every other caller.)
+      psnr, ssim, lpips     the means over the target views (lpips only with `lpips_net`); not in the distill-only variant, as in the reference
+      comparison            [3, Hc, Wc] f32: hcat of the vcat columns context | context depth | target | prediction | predicted depth
+                            (:614-620), or with distill_only (needs `distiller`, the teacher of distill_targets) context | teacher depth |
+                            teacher confidence | predicted depth | predicted confidence when the encoder returns one (:559-585)
+      projections           [3, P, 3 P'] f32 (projections=True, not distill_only): hcat of render_projections(gaussians, 256)[0] (:624-630)
+      video                 uint8 frames of render_video_interpolation_step (video=True, not distill_only; :696-704 render it for two views)
+    Out of scope: the wobble and exaggerated trajectories, the camera plot, text labels (add_label needs a font file), and the wandb, file
+    and mp4 output."""
+    from .misc import utils as viz
+    from .visualization import layout, validation_in_3d
+    ctx, tgt = batch["context"], batch["target"]
+    b, _, _, h, w = tgt["image"].shape
+    assert b == 1, "validation_step takes one scene, as the reference does"
+    if distill_only and distiller is None:
+        raise ValueError("validation_step(distill_only=True) needs the distiller")
+    model_outs = encoder(ctx, distill=True, compute_viewspace_depth=True) if distill_only else encoder(ctx, compute_viewspace_depth=True)
+    context_img = viz.inverse_normalize(ctx["image"][0])
+    out = {}
+    if distill_only:
+        gt1, gt2 = distiller(ctx, False)
+        pts1, pts2 = gt1["pts3d"], gt2["pts3d"]
+        c2w = ctx["extrinsics"][:, 1].float()
+        # the second view's points in its own camera: R^-1 (p - t), only the depth row; R is a rotation, the reference inverts it
+        rel = pts2 - c2w[:, None, None, :3, 3]
+        depth2 = (torch.linalg.inv_ex(c2w[:, :3, :3]).inverse[:, None, None, 2, :] * rel).sum(-1)
+        teacher_depth = viz.vis_depth_map(torch.cat([pts1[..., -1], depth2]))
+        teacher_conf = viz.confidence_map(torch.cat([gt1["conf"], gt2["conf"]]))
+        columns = [layout.vcat(*context_img), layout.vcat(*teacher_depth), layout.vcat(*teacher_conf),
+                   layout.vcat(*viz.vis_depth_map(model_outs["context_view_depths"][0]))]
+        if model_outs.get("confidence") is not None:
+            columns.append(layout.vcat(*viz.confidence_map(model_outs["confidence"][0])))
+        out["comparison"] = layout.hcat(*columns)
+        return out
+    gaussians = model_outs["gaussians"]
+    output = decoder.forward(gaussians, tgt["extrinsics"], tgt["intrinsics"], tgt["near"], tgt["far"], (h, w), "depth")
+    rgb_pred, rgb_gt = output.color[0], tgt["image"][0]
+    out["psnr"] = compute_psnr(rgb_gt, rgb_pred).mean()
+    out["ssim"] = compute_ssim(rgb_gt, rgb_pred).mean()
+    if lpips_net is not None:
+        out["lpips"] = compute_lpips(rgb_gt, rgb_pred, lpips_net).mean()
+    out["comparison"] = layout.hcat(layout.vcat(*context_img), layout.vcat(*viz.vis_depth_map(model_outs["context_view_depths"][0])),
+                                    layout.vcat(*rgb_gt), layout.vcat(*rgb_pred), layout.vcat(*viz.vis_depth_map(output.depth[0])))
+    if projections:
+        out["projections"] = layout.hcat(*validation_in_3d.render_projections(gaussians, 256, extra_label="")[0])
+    if video:
+        out["video"] = render_video_interpolation_step(lambda c, **kw: dict(gaussians=gaussians), decoder, batch)
+    return out

@@ -1,0 +1,1 @@
+"""The reference's src/misc, as far as it is built: utils (depth and confidence colour maps)."""

@@ -83,3 +83,44 @@ def render_cuda(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tenso
         means, covs, shs, opac = gaussian_means, gaussian_covariances, gaussian_sh_coefficients, gaussian_opacities
     return render_batched(extrinsics, intrinsics, near, far, image_shape, background_color, means, covs, shs, opac,
                           cam_scene, cam_rot_delta, cam_trans_delta, use_sh, sh_degree)
+
+
+def render_cuda_orthographic(extrinsics: Tensor, width: Tensor, height: Tensor, near: Tensor, far: Tensor, image_shape: tuple[int, int],
+                             background_color: Tensor, gaussian_means: Tensor, gaussian_covariances: Tensor,
+                             gaussian_sh_coefficients: Tensor, gaussian_opacities: Tensor, fov_degrees: float = 0.1, use_sh: bool = True,
+                             dump: dict | None = None) -> Tensor:
+    """Same signature and return as the reference's render_cuda_orthographic (cuda_splatting.py:242-333): an "orthographic" view faked by
+    a camera moved back along its axis until a field of view of `fov_degrees` spans `width`, one Gaussian set [b, g, ...] per camera,
+    images [b, 3, h, w].  As in the reference the projection matrix is built from fov_y = atan(2 tan_fov_y) while the rasterizer is handed
+    tan_fov_y itself.  All b cameras go through ONE rasterizer call (the reference loops, and its move_back assignment takes b == 1 only);
+    the 4 x 4 product with the move-back matrix is written out (it only shifts the position along the camera's z column).  `dump`, the
+    reference's escape hatch, receives the camera that is rendered: extrinsics, fov_x, fov_y, near, far."""
+    b = extrinsics.shape[0]
+    h, w = image_shape
+    assert use_sh or gaussian_sh_coefficients.shape[-1] == 1
+    degree = isqrt(gaussian_sh_coefficients.shape[-1]) - 1
+    # a pinhole of half-angle a = fov_degrees / 2 sees `width` at the distance width / (2 tan a): stand that far behind the given pose
+    half_x = torch.deg2rad(torch.tensor(0.5 * fov_degrees, dtype=torch.float32, device=extrinsics.device))
+    angle_x = 2 * half_x
+    tan_x = torch.tan(half_x)
+    back = width * 0.5 / tan_x
+    tan_y = height * 0.5 / back
+    angle_y = torch.atan(tan_y * 2)       # as the reference has it (not 2 atan tan_y): the projection matrix below is built from it
+    pose = extrinsics.float().clone()
+    pose[:, :, 3] -= back[:, None] * pose[:, :, 2]       # pose @ (identity with -back at [2, 3]): a step back along the camera's z
+    z_near, z_far = near + back, far + back
+    if dump is not None:
+        dump.update(extrinsics=pose, fov_x=angle_x, fov_y=angle_y, near=z_near, far=z_far)
+    proj_t = get_projection_matrix(z_near.float(), z_far.float(), angle_x.expand(b), angle_y).transpose(1, 2)
+    view_t = torch.linalg.inv_ex(pose).inverse.transpose(1, 2)       # (inv_ex: no check on the host, no synchronisation)
+    full_t = sum(view_t[:, :, k, None] * proj_t[:, k, None, :] for k in range(4))
+    tanfov = torch.stack([tan_x.expand(b), tan_y], dim=-1)
+    if use_sh:
+        kw = dict(shs=gaussian_sh_coefficients, sh_rgb_major=True)
+    else:
+        kw = dict(colors_precomp=gaussian_sh_coefficients[..., 0].contiguous())
+    color, _radii, _depth, _opacity, _touched = rasterize(
+        gaussian_means, gaussian_covariances, gaussian_opacities, view_t.reshape(b, 16).contiguous(), full_t.reshape(b, 16).contiguous(),
+        pose[:, :3, 3].contiguous(), tanfov.contiguous(), background_color, h, w, sh_degree=degree, cam_scene=None,
+        projmatrix_raw=proj_t.reshape(b, 16).contiguous(), **kw)
+    return color

@@ -1538,3 +1538,74 @@ def trajectory_metrics(pred: torch.Tensor, gt: torch.Tensor, delta: int = 1, ret
         L.call("vsm_trajectory_metrics", dev, L.ptr(pred.detach()), L.ptr(gt.detach()), _TRAJ_DTYPES[pred.dtype], B, V,
                min(int(delta), 2 ** 31 - 1), L.ptr(metrics), L.ptr(valid), L.ptr(align))
     return (metrics, valid, align) if return_alignment else (metrics, valid)
+
+
+# ---- visualisation (include/vicasplat_viz.h, csrc/viz.hip) ---------------------------------------------------------------------------
+def _viz_f32(name: str, t: torch.Tensor, what: str) -> torch.Tensor:
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"{name} takes a contiguous f32 {what}, got {t.dtype} with strides {t.stride()}")
+    return t.detach()
+
+
+def depth_range(values: torch.Tensor, return_order_stats: bool = False):
+    """range [2] f32 = (near, far) of vis_depth_map (src/misc/utils.py:13-22) for a contiguous f32 tensor of at most L.VSV_MAX_RANGE_N
+    values on a HIP device: far = log(Q_0.99(all values)), near = log(Q_0.01(the values > 0)) or 0 when none is, Q = torch.quantile
+    (vsv_depth_range; include/vicasplat_viz.h states the arithmetic).  return_order_stats: also [4] f32, the two order statistics of
+    near, then of far.  On the current stream, no host copy, no synchronisation."""
+    dev = L.require_device(values)
+    v = _viz_f32("depth_range", values, "tensor")
+    n = v.numel()
+    if n < 1:
+        raise ValueError("depth_range of an empty tensor (torch.quantile raises on one too)")
+    ws = torch.empty(int(L.call("vsv_depth_range_workspace_bytes", dev, n)), dtype=torch.uint8, device=dev)
+    out = torch.empty(2, dtype=torch.float32, device=dev)
+    stats = torch.empty(4, dtype=torch.float32, device=dev) if return_order_stats else None
+    L.call("vsv_depth_range", dev, L.ptr(v), n, L.ptr(out), L.ptr(stats), L.ptr(ws), ws.numel())
+    return (out, stats) if return_order_stats else out
+
+
+def color_map(value: torch.Tensor, lut: torch.Tensor, mode: int, value_range: Optional[torch.Tensor] = None,
+              out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """value [..., H, W] f32 -> [..., 3, H, W] f32 or uint8 colours through lut [256, 3] f32 (vsv_color_map).  mode L.VSV_MODE_DEPTH:
+    x = 1 - (log v - near) / (far - near) with value_range = (near, far) on the device; L.VSV_MODE_MAX: x = v / max(v).  The index is
+    min(trunc(clip(x, 0, 1) * 256), 255); a NaN x gives 0.  On the current stream, no host copy, no synchronisation."""
+    dev = L.require_device(value, lut, value_range)
+    v = _viz_f32("color_map", value, "value")
+    if v.dim() < 2:
+        raise ValueError(f"color_map takes [..., H, W], got {tuple(v.shape)}")
+    if tuple(lut.shape) != (256, 3):
+        raise ValueError(f"color_map takes a table [256, 3], got {tuple(lut.shape)}")
+    lut = _viz_f32("color_map", lut, "table")
+    if out_dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f"color_map writes f32 or uint8, got {out_dtype}")
+    if mode == L.VSV_MODE_DEPTH:
+        if value_range is None or value_range.numel() != 2:
+            raise ValueError("color_map in the depth mode takes value_range = (near, far) on the device")
+        value_range = _viz_f32("color_map", value_range, "value_range")
+    H, W = v.shape[-2:]
+    M = v.numel() // max(H * W, 1)
+    out = torch.empty(*v.shape[:-2], 3, H, W, dtype=out_dtype, device=dev)
+    nws = int(L.call("vsv_color_map_workspace_bytes", dev, mode))
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
+    if v.numel():
+        L.call("vsv_color_map", dev, L.ptr(v), M, H, W, mode, L.ptr(value_range), L.ptr(lut), L.ptr(out),
+               L.VSV_OUT_U8 if out_dtype == torch.uint8 else L.VSV_OUT_F32, L.ptr(ws), nws)
+    return out
+
+
+def video_frames(rgb: torch.Tensor, depth: torch.Tensor, value_range: torch.Tensor, lut: torch.Tensor, gap: int = 8) -> torch.Tensor:
+    """frames [M, 3, 2 H + gap, W] uint8 of render_video_generic (src/model/model_wrapper.py:805-813) in one launch: rgb [M, 3, H, W] f32
+    clipped and truncated to bytes, `gap` white rows, and depth [M, H, W] f32 through the depth colour map with value_range = (near, far)
+    and lut [256, 3] (vsv_video_frames).  A NaN gives 0.  On the current stream, no host copy, no synchronisation."""
+    dev = L.require_device(rgb, depth, value_range, lut)
+    rgb, depth = _viz_f32("video_frames", rgb, "rgb"), _viz_f32("video_frames", depth, "depth")
+    value_range, lut = _viz_f32("video_frames", value_range, "value_range"), _viz_f32("video_frames", lut, "table")
+    if rgb.dim() != 4 or rgb.shape[1] != 3 or depth.dim() != 3 or tuple(depth.shape) != (rgb.shape[0], rgb.shape[2], rgb.shape[3]):
+        raise ValueError(f"video_frames takes rgb [M, 3, H, W] and depth [M, H, W], got {tuple(rgb.shape)} and {tuple(depth.shape)}")
+    if tuple(lut.shape) != (256, 3) or value_range.numel() != 2 or int(gap) != gap or gap < 0:
+        raise ValueError("video_frames takes a table [256, 3], value_range = (near, far) and a gap >= 0")
+    M, _, H, W = rgb.shape
+    frames = torch.empty(M, 3, 2 * H + int(gap), W, dtype=torch.uint8, device=dev)
+    if frames.numel():
+        L.call("vsv_video_frames", dev, L.ptr(rgb), L.ptr(depth), M, H, W, int(gap), L.ptr(value_range), L.ptr(lut), L.ptr(frames))
+    return frames
