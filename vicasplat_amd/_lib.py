@@ -21,6 +21,7 @@ _TEACHER_HEADER = os.path.join(_HERE, "..", "include", "vicasplat_teacher.h")   
 _METRICS_HEADER = os.path.join(_HERE, "..", "include", "vicasplat_metrics.h")   # the fifth public header: the vsm_ entries (csrc/trajectory.hip)
 _DATA_HEADER = os.path.join(_HERE, "..", "include", "vicasplat_data.h")   # the sixth public header: the vsp_ entries (csrc/preprocess.hip)
 _VIZ_HEADER = os.path.join(_HERE, "..", "include", "vicasplat_viz.h")   # the seventh public header: the vsv_ entries (csrc/viz.hip)
+_OVERLAP_HEADER = os.path.join(_HERE, "..", "include", "vicasplat_overlap.h")   # the eighth public header: the vso_ entry (csrc/overlap.hip)
 _SO = os.environ.get("VICASPLAT_HIP_LIB") or os.path.join(_HERE, "libvicasplat_hip.so")   # (override: A/B runs of two builds)
 _lock = threading.Lock()
 ABI_VERSION = 10    # == vs_abi_version() of csrc/api.hip; INTEGRATION.md lists the entries of every version
@@ -48,6 +49,9 @@ _VSV = header_constants(_VIZ_HEADER, "VSV_")
 VSV_THREADS, VSV_VEC, VSV_MAX_BLOCKS, VSV_MAX_RANGE_N = _VSV["VSV_THREADS"], _VSV["VSV_VEC"], _VSV["VSV_MAX_BLOCKS"], _VSV["VSV_MAX_RANGE_N"]
 VSV_MODE_DEPTH, VSV_MODE_MAX, VSV_MODE_UNIT = _VSV["VSV_MODE_DEPTH"], _VSV["VSV_MODE_MAX"], _VSV["VSV_MODE_UNIT"]
 VSV_OUT_F32, VSV_OUT_U8 = _VSV["VSV_OUT_F32"], _VSV["VSV_OUT_U8"]
+# the launch geometry of the vso_ entry, as include/vicasplat_overlap.h defines it
+_VSO = header_constants(_OVERLAP_HEADER, "VSO_")
+VSO_THREADS, VSO_CHUNK = _VSO["VSO_THREADS"], _VSO["VSO_CHUNK"]
 
 AllocFn = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_int32, C.c_size_t)
 
@@ -82,7 +86,7 @@ def build(force: bool = False) -> str:
     src_dir = os.path.join(_HERE, "csrc")
     newest = max(os.path.getmtime(os.path.join(src_dir, f)) for f in os.listdir(src_dir)
                  if f.endswith((".hip", ".h", "Makefile")))
-    newest = max(newest, os.path.getmtime(_HEADER), os.path.getmtime(_DISTILL_HEADER), os.path.getmtime(_LOSS_HEADER), os.path.getmtime(_TEACHER_HEADER), os.path.getmtime(_METRICS_HEADER), os.path.getmtime(_DATA_HEADER), os.path.getmtime(_VIZ_HEADER))
+    newest = max(newest, os.path.getmtime(_HEADER), os.path.getmtime(_DISTILL_HEADER), os.path.getmtime(_LOSS_HEADER), os.path.getmtime(_TEACHER_HEADER), os.path.getmtime(_METRICS_HEADER), os.path.getmtime(_DATA_HEADER), os.path.getmtime(_VIZ_HEADER), os.path.getmtime(_OVERLAP_HEADER))
     if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < newest:
         subprocess.check_call(["make", "-C", src_dir, "-j8"], stdout=subprocess.DEVNULL)
     return _SO
@@ -96,12 +100,12 @@ _STRUCTS = {"VsRasterIn": VsRasterIn, "VsRasterOut": VsRasterOut, "VsRasterGrads
 
 def parse_header(text: str, prefix: str = "vs_") -> dict:
     """{name: (restype, [argtypes], takes_stream)} of every prototype in the text of include/vicasplat_hip.h (or, with prefix="vsd_", of
-    include/vicasplat_distill.h, with prefix="vsl_", of include/vicasplat_loss.h, with prefix="vst_", of include/vicasplat_teacher.h, with prefix="vsm_", of include/vicasplat_metrics.h, with prefix="vsp_", of include/vicasplat_data.h, with prefix="vsv_", of include/vicasplat_viz.h: every entry of a header carries the header's prefix).  The header is the one place
+    include/vicasplat_distill.h, with prefix="vsl_", of include/vicasplat_loss.h, with prefix="vst_", of include/vicasplat_teacher.h, with prefix="vsm_", of include/vicasplat_metrics.h, with prefix="vsp_", of include/vicasplat_data.h, with prefix="vsv_", of include/vicasplat_viz.h, with prefix="vso_", of include/vicasplat_overlap.h: every entry of a header carries the header's prefix).  The header is the one place
     where a signature is written down; a prototype or a type outside its small vocabulary raises with the prototype's text (ctypes'
     default conversion would truncate or shift the arguments silently)."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*|^\s*#[^\n]*", "", text, flags=re.S | re.M)
     text = re.sub(r'extern\s+"C"\s*\{|\b(?:typedef\s+struct|enum)\b[^{;]*\{[^}]*\}[^;]*;|\btypedef\b[^;{]*;', "", text)
-    header = {"vs_": "vicasplat_hip.h", "vsd_": "vicasplat_distill.h", "vsl_": "vicasplat_loss.h", "vst_": "vicasplat_teacher.h", "vsm_": "vicasplat_metrics.h", "vsp_": "vicasplat_data.h", "vsv_": "vicasplat_viz.h"}.get(prefix, f"header of the {prefix} entries")
+    header = {"vs_": "vicasplat_hip.h", "vsd_": "vicasplat_distill.h", "vsl_": "vicasplat_loss.h", "vst_": "vicasplat_teacher.h", "vsm_": "vicasplat_metrics.h", "vsp_": "vicasplat_data.h", "vsv_": "vicasplat_viz.h", "vso_": "vicasplat_overlap.h"}.get(prefix, f"header of the {prefix} entries")
     sigs = {}
     for proto in (" ".join(p.split()) for p in text.split(";")):
         if proto in ("", "}"):
@@ -156,6 +160,8 @@ def _load() -> C.CDLL:
                 sigs.update(parse_header(f.read(), prefix="vsp_"))
             with open(_VIZ_HEADER) as f:
                 sigs.update(parse_header(f.read(), prefix="vsv_"))
+            with open(_OVERLAP_HEADER) as f:
+                sigs.update(parse_header(f.read(), prefix="vso_"))
             for name, (restype, argtypes, takes_stream) in sigs.items():
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = restype, argtypes

@@ -30,3 +30,18 @@ def confidence_map(result: Tensor) -> Tensor:
     """result [*batch, H, W] f32 -> [*batch, 3, H, W] f32 `magma` colours of result / max(result)."""
     value = result.detach().float().contiguous()
     return ops.color_map(value, device_table("magma", value.device), L.VSV_MODE_MAX)
+
+
+def get_overlap_tag(overlap) -> str:
+    """The overlap class of an evaluation-index entry (src/misc/utils.py:38-48): "small" for [0.05, 0.3], "medium" up to 0.55, "large" up to
+    0.8, else "ignore" (an overlap below 0.05 falls through to "medium", as it does in the reference)."""
+    if 0.05 <= overlap <= 0.3:
+        overlap_tag = "small"
+    elif overlap <= 0.55:
+        overlap_tag = "medium"
+    elif overlap <= 0.8:
+        overlap_tag = "large"
+    else:
+        overlap_tag = "ignore"
+
+    return overlap_tag
