@@ -1,4 +1,4 @@
-"""ctypes binding of libvicasplat_hip.so (the C ABI declared in include/vicasplat_hip.h).
+"""ctypes binding of libvicasplat_hip.so (the C ABI declared in the public headers of include/, listed once in HEADERS).
 
 The product path has NO CPU fallback: if the shared library is missing or a tensor is not on a HIP device the
 call raises.  PyTorch is used only for device memory (caching allocator) and streams.
@@ -14,44 +14,47 @@ import threading
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_HEADER = os.path.join(_HERE, "..", "include", "vicasplat_hip.h")     # the one statement of every signature (parse_header)
-_DISTILL_HEADER = os.path.join(_HERE, "..", "include", "vicasplat_distill.h")   # the second public header: the vsd_ entries (csrc/distill.hip)
-_LOSS_HEADER = os.path.join(_HERE, "..", "include", "vicasplat_loss.h")   # the third public header: the vsl_ entries (csrc/depth_loss.hip)
-_TEACHER_HEADER = os.path.join(_HERE, "..", "include", "vicasplat_teacher.h")   # the fourth public header: the vst_ entries (csrc/teacher.hip)
-_METRICS_HEADER = os.path.join(_HERE, "..", "include", "vicasplat_metrics.h")   # the fifth public header: the vsm_ entries (csrc/trajectory.hip)
-_DATA_HEADER = os.path.join(_HERE, "..", "include", "vicasplat_data.h")   # the sixth public header: the vsp_ entries (csrc/preprocess.hip)
-_VIZ_HEADER = os.path.join(_HERE, "..", "include", "vicasplat_viz.h")   # the seventh public header: the vsv_ entries (csrc/viz.hip)
-_OVERLAP_HEADER = os.path.join(_HERE, "..", "include", "vicasplat_overlap.h")   # the eighth public header: the vso_ entry (csrc/overlap.hip)
+# Every public header of include/, as (prefix of its entries, file name), in the order the headers were added: the one statement of the list.
+# The signatures (parse_header), the integer constants (header_constants) and build()'s staleness check all read it.
+HEADERS = (
+    ("vs_", "vicasplat_hip.h"),          # the kernels of the model and the rasterizer; vs_abi_version, vs_last_error
+    ("vsd_", "vicasplat_distill.h"),     # csrc/distill.hip
+    ("vsl_", "vicasplat_loss.h"),        # csrc/depth_loss.hip
+    ("vst_", "vicasplat_teacher.h"),     # csrc/teacher.hip
+    ("vsm_", "vicasplat_metrics.h"),     # csrc/trajectory.hip
+    ("vsp_", "vicasplat_data.h"),        # csrc/preprocess.hip
+    ("vsv_", "vicasplat_viz.h"),         # csrc/viz.hip
+    ("vso_", "vicasplat_overlap.h"),     # csrc/overlap.hip
+)
+
+
+def header_path(prefix: str) -> str:
+    """The path of the public header whose entries carry `prefix`."""
+    return os.path.join(_HERE, "..", "include", dict(HEADERS)[prefix])
+
+
 _SO = os.environ.get("VICASPLAT_HIP_LIB") or os.path.join(_HERE, "libvicasplat_hip.so")   # (override: A/B runs of two builds)
 _lock = threading.Lock()
 ABI_VERSION = 10    # == vs_abi_version() of csrc/api.hip; INTEGRATION.md lists the entries of every version
 _lib = None
 _entries: dict = {}    # name -> (bound function, takes the stream as its last argument), filled by _load() from the header
 
-VS_BUF_GEOM, VS_BUF_RECT, VS_BUF_CLAMPED, VS_BUF_TILE_RANGES, VS_BUF_TILE_CURSOR, VS_BUF_KEYS, VS_BUF_POINT_LIST, \
-    VS_BUF_SORT_SCRATCH, VS_BUF_FINAL_T, VS_BUF_N_CONTRIB, VS_BUF_MISC, VS_BUF_DEPTH, VS_BUF_CHECKPOINT, VS_BUF_COUNT = range(14)
-VS_RASTER_COUNT_TOUCHED = 1
-VS_RASTER_SAVE_FOR_BACKWARD = 2
-VS_RASTER_SH_RGB_MAJOR = 4
-VS_RASTER_COV_3X3 = 8
-VS_SSIM_COMPONENTS = 1
-VS_SSIM_UNIT_WINDOW = 2
-
 
 def header_constants(path: str, prefix: str) -> dict:
-    """{name: value} of the integer `#define`s of a public header whose names carry `prefix`: the header states them once."""
+    """{name: value} of the integer constants of a public header whose names carry `prefix`, its `#define NAME <int>` lines and its enum
+    members written `NAME = <int>`: the header states them once."""
     with open(path) as f:
-        return {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define (%s\w+) (-?\d+)\s*$" % re.escape(prefix), f.read(), flags=re.M)}
+        text = f.read()
+    name = re.escape(prefix) + r"\w+"
+    consts = {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define (%s) (-?\d+)\s*$" % name, text, flags=re.M)}
+    for body in re.findall(r"\benum\b[^{;]*\{([^}]*)\}", re.sub(r"/\*.*?\*/|//[^\n]*", "", text, flags=re.S)):
+        consts.update((m.group(1), int(m.group(2))) for m in re.finditer(r"\b(%s)\s*=\s*(-?\d+)\s*(?:,|$)" % name, body))
+    return consts
 
 
-# the launch geometry, the size limit, the modes and the output types of the vsv_ entries, as include/vicasplat_viz.h defines them
-_VSV = header_constants(_VIZ_HEADER, "VSV_")
-VSV_THREADS, VSV_VEC, VSV_MAX_BLOCKS, VSV_MAX_RANGE_N = _VSV["VSV_THREADS"], _VSV["VSV_VEC"], _VSV["VSV_MAX_BLOCKS"], _VSV["VSV_MAX_RANGE_N"]
-VSV_MODE_DEPTH, VSV_MODE_MAX, VSV_MODE_UNIT = _VSV["VSV_MODE_DEPTH"], _VSV["VSV_MODE_MAX"], _VSV["VSV_MODE_UNIT"]
-VSV_OUT_F32, VSV_OUT_U8 = _VSV["VSV_OUT_F32"], _VSV["VSV_OUT_U8"]
-# the launch geometry of the vso_ entry, as include/vicasplat_overlap.h defines it
-_VSO = header_constants(_OVERLAP_HEADER, "VSO_")
-VSO_THREADS, VSO_CHUNK = _VSO["VSO_THREADS"], _VSO["VSO_CHUNK"]
+# every integer constant of every public header, under the header's own name: VS_BUF_*, VS_RASTER_*, VS_SSIM_*, VSP_*, VSV_*, VSO_*
+for _prefix, _ in HEADERS:
+    globals().update(header_constants(header_path(_prefix), _prefix.upper()))
 
 AllocFn = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_int32, C.c_size_t)
 
@@ -86,7 +89,7 @@ def build(force: bool = False) -> str:
     src_dir = os.path.join(_HERE, "csrc")
     newest = max(os.path.getmtime(os.path.join(src_dir, f)) for f in os.listdir(src_dir)
                  if f.endswith((".hip", ".h", "Makefile")))
-    newest = max(newest, os.path.getmtime(_HEADER), os.path.getmtime(_DISTILL_HEADER), os.path.getmtime(_LOSS_HEADER), os.path.getmtime(_TEACHER_HEADER), os.path.getmtime(_METRICS_HEADER), os.path.getmtime(_DATA_HEADER), os.path.getmtime(_VIZ_HEADER), os.path.getmtime(_OVERLAP_HEADER))
+    newest = max(newest, *(os.path.getmtime(header_path(prefix)) for prefix, _ in HEADERS))
     if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < newest:
         subprocess.check_call(["make", "-C", src_dir, "-j8"], stdout=subprocess.DEVNULL)
     return _SO
@@ -99,13 +102,12 @@ _STRUCTS = {"VsRasterIn": VsRasterIn, "VsRasterOut": VsRasterOut, "VsRasterGrads
 
 
 def parse_header(text: str, prefix: str = "vs_") -> dict:
-    """{name: (restype, [argtypes], takes_stream)} of every prototype in the text of include/vicasplat_hip.h (or, with prefix="vsd_", of
-    include/vicasplat_distill.h, with prefix="vsl_", of include/vicasplat_loss.h, with prefix="vst_", of include/vicasplat_teacher.h, with prefix="vsm_", of include/vicasplat_metrics.h, with prefix="vsp_", of include/vicasplat_data.h, with prefix="vsv_", of include/vicasplat_viz.h, with prefix="vso_", of include/vicasplat_overlap.h: every entry of a header carries the header's prefix).  The header is the one place
-    where a signature is written down; a prototype or a type outside its small vocabulary raises with the prototype's text (ctypes'
-    default conversion would truncate or shift the arguments silently)."""
+    """{name: (restype, [argtypes], takes_stream)} of every prototype in the text of the header whose entries carry `prefix` (HEADERS).  The
+    header is the one place where a signature is written down; a prototype without the prefix, or a type outside the small vocabulary
+    below, raises with the prototype's text (ctypes' default conversion would truncate or shift the arguments silently)."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*|^\s*#[^\n]*", "", text, flags=re.S | re.M)
     text = re.sub(r'extern\s+"C"\s*\{|\b(?:typedef\s+struct|enum)\b[^{;]*\{[^}]*\}[^;]*;|\btypedef\b[^;{]*;', "", text)
-    header = {"vs_": "vicasplat_hip.h", "vsd_": "vicasplat_distill.h", "vsl_": "vicasplat_loss.h", "vst_": "vicasplat_teacher.h", "vsm_": "vicasplat_metrics.h", "vsp_": "vicasplat_data.h", "vsv_": "vicasplat_viz.h", "vso_": "vicasplat_overlap.h"}.get(prefix, f"header of the {prefix} entries")
+    header = dict(HEADERS).get(prefix, f"header of the {prefix} entries")
     sigs = {}
     for proto in (" ".join(p.split()) for p in text.split(";")):
         if proto in ("", "}"):
@@ -146,22 +148,10 @@ def _load() -> C.CDLL:
             L = C.CDLL(_SO)
             if L.vs_abi_version() != ABI_VERSION:     # the ctypes mirrors of the structs above are for exactly this layout
                 raise RuntimeError(f"{_SO} has ABI version {L.vs_abi_version()}, this package needs {ABI_VERSION}: rebuild it (python -c 'import __graft_entry__ as g; g.build()')")
-            with open(_HEADER) as f:
-                sigs = parse_header(f.read())
-            with open(_DISTILL_HEADER) as f:
-                sigs.update(parse_header(f.read(), prefix="vsd_"))
-            with open(_LOSS_HEADER) as f:
-                sigs.update(parse_header(f.read(), prefix="vsl_"))
-            with open(_TEACHER_HEADER) as f:
-                sigs.update(parse_header(f.read(), prefix="vst_"))
-            with open(_METRICS_HEADER) as f:
-                sigs.update(parse_header(f.read(), prefix="vsm_"))
-            with open(_DATA_HEADER) as f:
-                sigs.update(parse_header(f.read(), prefix="vsp_"))
-            with open(_VIZ_HEADER) as f:
-                sigs.update(parse_header(f.read(), prefix="vsv_"))
-            with open(_OVERLAP_HEADER) as f:
-                sigs.update(parse_header(f.read(), prefix="vso_"))
+            sigs = {}
+            for prefix, _ in HEADERS:
+                with open(header_path(prefix)) as f:
+                    sigs.update(parse_header(f.read(), prefix=prefix))
             for name, (restype, argtypes, takes_stream) in sigs.items():
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = restype, argtypes

@@ -28,8 +28,8 @@ from ... import _lib as L
 
 MIRROR_KEY = "mirror"      # views[MIRROR_KEY]: uint8 [*batch], 1 = mirror this view left-right in the crop shim
 PRECISION_BITS = 22        # PIL's 8-bit resample: 32 - 8 - 2
-MAX_TAPS = 128             # VSP_MAX_TAPS of include/vicasplat_data.h
-LAYOUT_U8_HWC, LAYOUT_U8_CHW, LAYOUT_F32_CHW = 0, 1, 2
+MAX_TAPS = L.VSP_MAX_TAPS  # the tap limit and the layout codes are include/vicasplat_data.h's
+LAYOUT_U8_HWC, LAYOUT_U8_CHW, LAYOUT_F32_CHW = L.VSP_LAYOUT_U8_HWC, L.VSP_LAYOUT_U8_CHW, L.VSP_LAYOUT_F32_CHW
 
 
 def _sinc(x: float) -> float:
