@@ -1,4 +1,4 @@
-"""ctypes binding of libvicasplat_hip.so (the C ABI declared in the public headers of include/, listed once in HEADERS).
+"""ctypes binding of libvicasplat_hip.so (the C ABI declared in the public headers of include/, listed once in HEADERS and DATA_HEADERS).
 
 The product path has NO CPU fallback: if the shared library is missing or a tensor is not on a HIP device the
 call raises.  PyTorch is used only for device memory (caching allocator) and streams.
@@ -26,11 +26,17 @@ HEADERS = (
     ("vsv_", "vicasplat_viz.h"),         # csrc/viz.hip
     ("vso_", "vicasplat_overlap.h"),     # csrc/overlap.hip
 )
+# The headers added beside that family without a change of the ABI version: the same library, parser and binding; HEADERS and its pinned
+# entry counts stay as they are.
+DATA_HEADERS = (
+    ("vsj_", "vicasplat_jpeg.h"),        # csrc/jpeg.hip, csrc/jpeg_decode.h
+)
+ALL_HEADERS = HEADERS + DATA_HEADERS
 
 
 def header_path(prefix: str) -> str:
     """The path of the public header whose entries carry `prefix`."""
-    return os.path.join(_HERE, "..", "include", dict(HEADERS)[prefix])
+    return os.path.join(_HERE, "..", "include", dict(ALL_HEADERS)[prefix])
 
 
 _SO = os.environ.get("VICASPLAT_HIP_LIB") or os.path.join(_HERE, "libvicasplat_hip.so")   # (override: A/B runs of two builds)
@@ -52,8 +58,8 @@ def header_constants(path: str, prefix: str) -> dict:
     return consts
 
 
-# every integer constant of every public header, under the header's own name: VS_BUF_*, VS_RASTER_*, VS_SSIM_*, VSP_*, VSV_*, VSO_*
-for _prefix, _ in HEADERS:
+# every integer constant of every public header, under the header's own name: VS_BUF_*, VS_RASTER_*, VS_SSIM_*, VSP_*, VSV_*, VSO_*, VSJ_*
+for _prefix, _ in ALL_HEADERS:
     globals().update(header_constants(header_path(_prefix), _prefix.upper()))
 
 AllocFn = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_int32, C.c_size_t)
@@ -89,7 +95,7 @@ def build(force: bool = False) -> str:
     src_dir = os.path.join(_HERE, "csrc")
     newest = max(os.path.getmtime(os.path.join(src_dir, f)) for f in os.listdir(src_dir)
                  if f.endswith((".hip", ".h", "Makefile")))
-    newest = max(newest, *(os.path.getmtime(header_path(prefix)) for prefix, _ in HEADERS))
+    newest = max(newest, *(os.path.getmtime(header_path(prefix)) for prefix, _ in ALL_HEADERS))
     if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < newest:
         subprocess.check_call(["make", "-C", src_dir, "-j8"], stdout=subprocess.DEVNULL)
     return _SO
@@ -107,7 +113,7 @@ def parse_header(text: str, prefix: str = "vs_") -> dict:
     below, raises with the prototype's text (ctypes' default conversion would truncate or shift the arguments silently)."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*|^\s*#[^\n]*", "", text, flags=re.S | re.M)
     text = re.sub(r'extern\s+"C"\s*\{|\b(?:typedef\s+struct|enum)\b[^{;]*\{[^}]*\}[^;]*;|\btypedef\b[^;{]*;', "", text)
-    header = dict(HEADERS).get(prefix, f"header of the {prefix} entries")
+    header = dict(ALL_HEADERS).get(prefix, f"header of the {prefix} entries")
     sigs = {}
     for proto in (" ".join(p.split()) for p in text.split(";")):
         if proto in ("", "}"):
@@ -149,7 +155,7 @@ def _load() -> C.CDLL:
             if L.vs_abi_version() != ABI_VERSION:     # the ctypes mirrors of the structs above are for exactly this layout
                 raise RuntimeError(f"{_SO} has ABI version {L.vs_abi_version()}, this package needs {ABI_VERSION}: rebuild it (python -c 'import __graft_entry__ as g; g.build()')")
             sigs = {}
-            for prefix, _ in HEADERS:
+            for prefix, _ in ALL_HEADERS:
                 with open(header_path(prefix)) as f:
                     sigs.update(parse_header(f.read(), prefix=prefix))
             for name, (restype, argtypes, takes_stream) in sigs.items():

@@ -1,12 +1,15 @@
 """The data side on the HIP path: what turns frames as a dataset delivers them into the batch the encoder and callers.training_step take.
 
 Built: the two shims every loader of the reference ends in (shims.augmentation_shim, shims.crop_shim) and `preprocess_batch`, which applies
-them to a collated batch with one launch per view group.  Not built: JPEG decoding, the dataset readers and the view samplers.
+them to a collated batch with one launch per view group; and the decode they start from (jpeg): `decode_jpeg_batch` turns the JPEG frames
+of a chunk into the packed uint8 buffer the crop shim reads, byte for byte PIL's pixels, and `convert_images` is the reference's function of
+that name.  Not built: the dataset readers and the view samplers.
 """
 from __future__ import annotations
 
 import torch
 
+from .jpeg import JpegError, convert_images, decode_jpeg_batch, pack_jpeg_batch  # noqa: F401
 from .shims.augmentation_shim import apply_augmentation_shim, draw_augmentation, reflect_extrinsics, reflect_views  # noqa: F401
 from .shims.crop_shim import MIRROR_KEY, apply_crop_shim, apply_crop_shim_to_views, center_crop, rescale, rescale_and_crop, resample_tables  # noqa: F401
 
