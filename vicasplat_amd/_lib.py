@@ -1,4 +1,4 @@
-"""ctypes binding of libvicasplat_hip.so (the C ABI declared in the public headers of include/, listed once in HEADERS and DATA_HEADERS).
+"""ctypes binding of libvicasplat_hip.so (the C ABI declared in the public headers of include/, listed once in HEADERS, DATA_HEADERS and DRAW_HEADERS).
 
 The product path has NO CPU fallback: if the shared library is missing or a tensor is not on a HIP device the
 call raises.  PyTorch is used only for device memory (caching allocator) and streams.
@@ -31,7 +31,11 @@ HEADERS = (
 DATA_HEADERS = (
     ("vsj_", "vicasplat_jpeg.h"),        # csrc/jpeg.hip, csrc/jpeg_decode.h
 )
-ALL_HEADERS = HEADERS + DATA_HEADERS
+# The presentation layer's header, added the same way (a table of its own: DATA_HEADERS is the data path's and stays as it is).
+DRAW_HEADERS = (
+    ("vsg_", "vicasplat_draw.h"),        # csrc/draw.hip
+)
+ALL_HEADERS = HEADERS + DATA_HEADERS + DRAW_HEADERS
 
 
 def header_path(prefix: str) -> str:
@@ -58,7 +62,7 @@ def header_constants(path: str, prefix: str) -> dict:
     return consts
 
 
-# every integer constant of every public header, under the header's own name: VS_BUF_*, VS_RASTER_*, VS_SSIM_*, VSP_*, VSV_*, VSO_*, VSJ_*
+# every integer constant of every public header, under the header's own name: VS_BUF_*, VS_RASTER_*, VS_SSIM_*, VSP_*, VSV_*, VSO_*, VSJ_*, VSG_*
 for _prefix, _ in ALL_HEADERS:
     globals().update(header_constants(header_path(_prefix), _prefix.upper()))
 

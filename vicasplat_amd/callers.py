@@ -26,6 +26,8 @@ scripts do around the encoder/decoder:
     csrc/trajectory.hip, batched over scenes, device tensors out
   * `test_step` — ModelWrapper.test_step, src/model/model_wrapper.py:323-381: the six numbers it logs, per scene, batched
   * `pose_eval_step` — PoseEvaluator.test_step, src/evaluation/pose_evaluator.py:77-174: the pose metrics before and after refinement
+  * `render_video_wobble_step`, `render_video_interpolation_exaggerated_step`, `camera_trajectory_plot` — model_wrapper.py:685-707, 733-773 and
+    the stated substitute for the plotly camera figure of :668-679, on csrc/draw.hip (visualization/drawing, camera_trajectory/wobble.py)
   * `validation_step`, `render_video_generic`, `render_video_interpolation_step`, `depth_video_frames` — ModelWrapper.validation_step and
     render_video_generic / render_video_interpolation (model_wrapper.py:524-704, 710-730, 776-815): metrics, the comparison image, the
     projections and the uint8 video frames as device tensors, on csrc/viz.hip (depth range, colour maps, frames)
@@ -1158,7 +1160,30 @@ def depth_video_frames(color: Tensor, depth: Tensor, gap: int = 8) -> Tensor:
     from . import ops
     from .visualization.color_map import device_table
     depth = depth.detach().float().contiguous()
-    return ops.video_frames(color.detach().float().contiguous(), depth, ops.depth_range(depth), device_table("turbo", depth.device), gap)
+    return ops.video_frames(color.detach().float().contiguous(), depth, sliced_depth_range(depth), device_table("turbo", depth.device), gap)
+
+
+def first_positives(flat: Tensor, limit: int) -> Tensor:
+    """[limit]: the first `limit` values > 0 of flat [n], in order, then zeros -- flat[flat > 0][:limit] at a fixed size, so that nothing is
+    read back to the host: every positive value is scattered to its rank, the ones past the limit (and everything else) to a spare slot."""
+    positive = flat > 0
+    rank = positive.cumsum(0) - 1
+    slot = torch.where(positive & (rank < limit), rank, torch.full_like(rank, limit))
+    return torch.zeros(limit + 1, dtype=flat.dtype, device=flat.device).scatter_(0, slot, flat)[:limit]
+
+
+def sliced_depth_range(depth: Tensor) -> Tensor:
+    """(near, far) [2] of vis_depth_map (src/misc/utils.py:13-22) for any number of values: ops.depth_range itself up to its limit of
+    VSV_MAX_RANGE_N = 16 000 000 values; beyond it (the 300 frames of the exaggerated video at 256 x 256) the reference's two slices -- far
+    over the first 16 000 000 values, near over the first 16 000 000 positive ones -- each formed at a fixed size and handed to the same kernel."""
+    from . import _lib, ops
+    limit = _lib.VSV_MAX_RANGE_N
+    flat = depth.reshape(-1)
+    if flat.numel() <= limit:
+        return ops.depth_range(depth)
+    far = ops.depth_range(flat[:limit].contiguous())[1]
+    near = ops.depth_range(first_positives(flat, limit))[0]
+    return torch.stack((near, far))
 
 
 @torch.no_grad()
@@ -1199,9 +1224,59 @@ def render_video_interpolation_step(encoder, decoder, batch: dict, **kw) -> Tens
     return render_video_generic(encoder, decoder, batch, trajectory_fn, **kw)
 
 
+def render_video_wobble_step(encoder, decoder, batch: dict, **kw) -> Tensor:
+    """ModelWrapper.render_video_wobble (model_wrapper.py:685-707): 60 frames of the first context camera on a spiral in its own image
+    plane that opens to a quarter of the distance between the first and the last context camera (camera_trajectory/wobble.py)."""
+    from .visualization.camera_trajectory.wobble import generate_wobble
+    ctx = batch["context"]
+
+    def trajectory_fn(t):
+        delta = (ctx["extrinsics"][:, 0, :3, 3] - ctx["extrinsics"][:, -1, :3, 3]).norm(dim=-1)
+        return (generate_wobble(ctx["extrinsics"][:, 0].float(), delta * 0.25, t),
+                ctx["intrinsics"][:, 0, None].float().expand(-1, t.shape[0], -1, -1))
+
+    return render_video_generic(encoder, decoder, batch, trajectory_fn, **{"num_frames": 60, **kw})
+
+
+def render_video_interpolation_exaggerated_step(encoder, decoder, batch: dict, **kw) -> Tensor:
+    """ModelWrapper.render_video_interpolation_exaggerated (model_wrapper.py:733-773): 300 frames, not eased and not looped, along the
+    interpolation between the first and the last context camera of scene 0 carried two intervals beyond either end (t * 5 - 2), each pose
+    followed by five turns on a circle of half the cameras' distance in its image plane."""
+    from .visualization.camera_trajectory.wobble import generate_wobble_transformation
+    ctx = batch["context"]
+
+    def trajectory_fn(t):
+        delta = (ctx["extrinsics"][:, 0, :3, 3] - ctx["extrinsics"][:, -1, :3, 3]).norm(dim=-1)
+        tf = generate_wobble_transformation(delta * 0.5, t, 5, scale_radius_with_t=False)
+        s = t * 5 - 2
+        return (interpolate_extrinsics(ctx["extrinsics"][:1, 0], ctx["extrinsics"][:1, -1], s) @ tf[:1],
+                interpolate_intrinsics(ctx["intrinsics"][:1, 0].float(), ctx["intrinsics"][:1, -1].float(), s))
+
+    return render_video_generic(encoder, decoder, batch, trajectory_fn, **{"num_frames": 300, "smooth": False, "loop_reverse": False, **kw})
+
+
+CAMERA_PLOT_GT_COLOR = (0.0, 0.75, 0.0)      # ground truth in green, prediction in red
+CAMERA_PLOT_PRED_COLOR = (1.0, 0.0, 0.0)
+
+
+def camera_trajectory_plot(gt_extrinsics: Tensor, gt_intrinsics: Tensor, pred_extrinsics: Tensor, pred_intrinsics: Tensor,
+                           resolution: int = 256) -> Tensor:
+    """[3, R, 3 R] f32: the ground-truth cameras [V, 4, 4] / [V, 3, 3] and the predicted ones in two colours, drawn by draw_cameras and seen
+    along the three axes side by side.  A STATED SUBSTITUTE for the plotly / pytorch3d figure of model_wrapper.py:668-679
+    (create_plotly_cameras_visualization), which is not built: the same information -- where the predicted trajectory leaves the true
+    one -- as three orthographic views instead of one perspective view, without axes and without a dashed line style."""
+    from .visualization import layout
+    from .visualization.drawing import draw_cameras
+    n_gt, n_pred = gt_extrinsics.shape[0], pred_extrinsics.shape[0]
+    color = torch.tensor([CAMERA_PLOT_GT_COLOR] * n_gt + [CAMERA_PLOT_PRED_COLOR] * n_pred, dtype=torch.float32, device=gt_extrinsics.device)
+    views = draw_cameras(resolution, torch.cat((gt_extrinsics.float(), pred_extrinsics.float())),
+                         torch.cat((gt_intrinsics.float(), pred_intrinsics.float())), color)
+    return layout.hcat(*views, gap=0)
+
+
 @torch.no_grad()
 def validation_step(encoder, decoder, batch: dict, *, lpips_net: LpipsVgg | None = None, distiller=None, distill_only: bool = False,
-                    video: bool = True, projections: bool = True) -> dict:
+                    video: bool = True, projections: bool = True, cameras: bool = False, extended_visualization: bool = False) -> dict:
     """ModelWrapper.validation_step (model_wrapper.py:524-704) for a batch of one scene, as device tensors: no .item() and no host copy of
     a result here or in the visualisation functions it calls.  (The decoder's camera set-up, `camera_matrices`, inverts the poses with
     torch.linalg.inv, which looks at its status on the host: rendering waits for the device there, as it does in every other caller.)
@@ -1211,8 +1286,16 @@ def validation_step(encoder, decoder, batch: dict, *, lpips_net: LpipsVgg | None
                             teacher confidence | predicted depth | predicted confidence when the encoder returns one (:559-585)
       projections           [3, P, 3 P'] f32 (projections=True, not distill_only): hcat of render_projections(gaussians, 256)[0] (:624-630)
       video                 uint8 frames of render_video_interpolation_step (video=True, not distill_only; :696-704 render it for two views)
-    Out of scope: the wobble and exaggerated trajectories, the camera plot, text labels (add_label needs a font file), and the wandb, file
-    and mp4 output."""
+      cameras               [3, 256, 3 * 256 + 16] f32 (cameras=True, not distill_only): hcat of render_cameras(batch, 256), the context and
+                            target cameras with their near and far planes (validation_in_3d.py:100-122)
+      camera_traj           [3, 256, 3 * 256] f32 (cameras=True, not distill_only): camera_trajectory_plot of the context cameras against
+                            model_outs["gaussian_camera_extrins"] / ["gaussian_camera_intrins"] (the context intrinsics when the encoder
+                            returns none), the stated substitute for the plotly figure of :658-679
+      video_exaggerated     uint8 frames of render_video_interpolation_exaggerated_step (extended_visualization=True and video=True, not
+                            distill_only; :647-648)
+    Both options are off by default, and every other output is the same with and without them.  render_video_wobble_step is built but, as
+    in the reference (:646), not called here.
+    Out of scope: text labels (add_label needs a font file), the plotly figure itself, and the wandb, file and mp4 output."""
     from .misc import utils as viz
     from .visualization import layout, validation_in_3d
     ctx, tgt = batch["context"], batch["target"]
@@ -1251,4 +1334,11 @@ def validation_step(encoder, decoder, batch: dict, *, lpips_net: LpipsVgg | None
         out["projections"] = layout.hcat(*validation_in_3d.render_projections(gaussians, 256, extra_label="")[0])
     if video:
         out["video"] = render_video_interpolation_step(lambda c, **kw: dict(gaussians=gaussians), decoder, batch)
+        if extended_visualization:
+            out["video_exaggerated"] = render_video_interpolation_exaggerated_step(lambda c, **kw: dict(gaussians=gaussians), decoder, batch)
+    if cameras:
+        out["cameras"] = layout.hcat(*validation_in_3d.render_cameras(batch, 256))
+        pred_intrinsics = model_outs.get("gaussian_camera_intrins")
+        out["camera_traj"] = camera_trajectory_plot(ctx["extrinsics"][0], ctx["intrinsics"][0], model_outs["gaussian_camera_extrins"][0],
+                                                    ctx["intrinsics"][0] if pred_intrinsics is None else pred_intrinsics[0])
     return out

@@ -1609,3 +1609,52 @@ def video_frames(rgb: torch.Tensor, depth: torch.Tensor, value_range: torch.Tens
     if frames.numel():
         L.call("vsv_video_frames", dev, L.ptr(rgb), L.ptr(depth), M, H, W, int(gap), L.ptr(value_range), L.ptr(lut), L.ptr(frames))
     return frames
+
+
+# ---- vector drawing (include/vicasplat_draw.h, csrc/draw.hip) --------------------------------------------------------------------------
+_DRAW_CAPS = {"butt": L.VSG_CAP_BUTT, "round": L.VSG_CAP_ROUND, "square": L.VSG_CAP_SQUARE}
+
+
+def _draw(entry: str, what: str, floats: int, image: torch.Tensor, prims: torch.Tensor, prim_offsets: torch.Tensor, num_passes: int,
+          out: Optional[torch.Tensor], extra: tuple) -> torch.Tensor:
+    dev = L.require_device(image, prims, prim_offsets, out)
+    image = _viz_f32(what, image, "image")
+    prims = _viz_f32(what, prims, "record array")
+    if image.dim() != 4 or image.shape[1] != 3:
+        raise ValueError(f"{what} takes images [B, 3, H, W], got {tuple(image.shape)}")
+    B, _, H, W = image.shape
+    if prims.dim() != 2 or prims.shape[1] != floats:
+        raise ValueError(f"{what} takes records [n, {floats}], got {tuple(prims.shape)}")
+    if prim_offsets.dtype != torch.int32 or tuple(prim_offsets.shape) != (B + 1,) or not prim_offsets.is_contiguous():
+        raise ValueError(f"{what} takes prim_offsets [B + 1 = {B + 1}] int32, got {tuple(prim_offsets.shape)} {prim_offsets.dtype}")
+    if H > L.VSG_MAX_SIDE or W > L.VSG_MAX_SIDE or B > L.VSG_MAX_BATCH:
+        raise ValueError(f"{what}: images of {H} x {W} in a batch of {B} exceed {L.VSG_MAX_SIDE} a side or {L.VSG_MAX_BATCH} images")
+    if num_passes not in (0, 1):
+        raise NotImplementedError(f"{what}: num_passes = {num_passes!r}: the HIP kernel refines once at the most (0 or 1)")
+    if out is None:
+        out = torch.empty_like(image)
+    elif out.shape != image.shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"{what}: out must be a contiguous f32 tensor of shape {tuple(image.shape)}, got {tuple(out.shape)} {out.dtype}")
+    if image.numel():
+        L.call(entry, dev, L.ptr(image), L.ptr(out), B, H, W, L.ptr(prims) if prims.numel() else None, prims.shape[0], L.ptr(prim_offsets),
+               *extra, int(num_passes))
+    return out
+
+
+def draw_lines(image: torch.Tensor, lines: torch.Tensor, prim_offsets: torch.Tensor, cap: str = "round", num_passes: int = 1,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One layer of antialiased lines over image [B, 3, H, W] f32 -> out of the same shape (vsg_draw_lines).  lines [n, L.VSG_LINE_FLOATS]
+    f32 IN PIXEL SPACE: start x, y, end x, y, width, r, g, b; prim_offsets [B + 1] int32 on the device gives image b the records
+    [off[b], off[b + 1]).  The topmost record is the highest-indexed one; cap is "butt", "round" or "square"; num_passes 0 samples the pixel
+    centres, 1 also refines every pixel that differs from a neighbour on an 8 x 8 grid.  An image without records is copied.  out may be
+    `image` itself.  include/vicasplat_draw.h states the arithmetic.  One launch on the current stream, no workspace, no synchronisation."""
+    if cap not in _DRAW_CAPS:
+        raise ValueError(f"draw_lines: cap {cap!r} is none of {sorted(_DRAW_CAPS)}")
+    return _draw("vsg_draw_lines", "draw_lines", L.VSG_LINE_FLOATS, image, lines, prim_offsets, num_passes, out, (_DRAW_CAPS[cap],))
+
+
+def draw_points(image: torch.Tensor, points: torch.Tensor, prim_offsets: torch.Tensor, num_passes: int = 1,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One layer of points (rings) over image [B, 3, H, W] f32 (vsg_draw_points): points [n, L.VSG_POINT_FLOATS] f32 in pixel space:
+    x, y, radius, inner radius, r, g, b; a sample is covered when inner <= |p - c| <= radius.  Everything else as draw_lines."""
+    return _draw("vsg_draw_points", "draw_points", L.VSG_POINT_FLOATS, image, points, prim_offsets, num_passes, out, ())

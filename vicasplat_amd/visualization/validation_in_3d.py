@@ -1,5 +1,6 @@
 """render_projections of the reference's src/visualization/validation_in_3d.py:25-97 with compute_equal_aabb_with_margin
-(src/visualization/drawing/cameras.py:272-284): the scene's Gaussians seen along the three axes through render_cuda_orthographic.
+(src/visualization/drawing/cameras.py:272-284): the scene's Gaussians seen along the three axes through render_cuda_orthographic; and
+render_cameras (:100-122): the context cameras (white) and the target cameras (red) of scene 0 as a camera plot (drawing/cameras.py).
 
 Stated deviation: text labels need a font file that is not available, so draw_label defaults to False here (True in the reference) and
 draw_label=True raises.  The three projections have one size, so the reference's padding to a common shape is the identity.
@@ -43,3 +44,15 @@ def render_projections(gaussians: Gaussians, resolution: int, margin: float = 0.
         views.append(render_cuda_orthographic(pose, side[:, axes[0]], side[:, axes[1]], torch.zeros_like(side[:, look]), side[:, look],
                                               (resolution, resolution), black, means, covs, shs, opac, fov_degrees=10.0))
     return torch.stack(views, dim=1)
+
+
+def render_cameras(batch: dict, resolution: int) -> Tensor:
+    """-> [3 (projection along x, y, z), 3, resolution, resolution]: draw_cameras over the context views, in white, followed by the target
+    views, in red, of the batch's first scene, with their near and far planes."""
+    from .drawing.cameras import draw_cameras      # (drawing.cameras imports this module for the AABB)
+    ctx, tgt = batch["context"], batch["target"]
+    n_ctx, n_tgt = ctx["extrinsics"].shape[1], tgt["extrinsics"].shape[1]
+    color = torch.ones((n_ctx + n_tgt, 3), dtype=torch.float32, device=tgt["extrinsics"].device)
+    color[n_ctx:, 1:] = 0
+    both = lambda key: torch.cat((ctx[key][0], tgt[key][0]))
+    return draw_cameras(resolution, both("extrinsics"), both("intrinsics"), color, both("near"), both("far"))
