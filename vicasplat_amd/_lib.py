@@ -1,4 +1,4 @@
-"""ctypes binding of libvicasplat_hip.so (the C ABI declared in the public headers of include/, listed once in HEADERS, DATA_HEADERS and DRAW_HEADERS).
+"""ctypes binding of libvicasplat_hip.so (the C ABI declared in the public headers of include/, listed once in HEADERS, DATA_HEADERS, DRAW_HEADERS and IO_HEADERS).
 
 The product path has NO CPU fallback: if the shared library is missing or a tensor is not on a HIP device the
 call raises.  PyTorch is used only for device memory (caching allocator) and streams.
@@ -36,11 +36,16 @@ DRAW_HEADERS = (
     ("vsg_", "vicasplat_draw.h"),        # csrc/draw.hip
 )
 ALL_HEADERS = HEADERS + DATA_HEADERS + DRAW_HEADERS
+# The file-output header, added the same way once more; ALL_HEADERS is pinned as the three tables above, so the binding runs over BOUND_HEADERS.
+IO_HEADERS = (
+    ("vse_", "vicasplat_png.h"),         # csrc/png.hip, csrc/png_deflate.h
+)
+BOUND_HEADERS = ALL_HEADERS + IO_HEADERS
 
 
 def header_path(prefix: str) -> str:
     """The path of the public header whose entries carry `prefix`."""
-    return os.path.join(_HERE, "..", "include", dict(ALL_HEADERS)[prefix])
+    return os.path.join(_HERE, "..", "include", dict(BOUND_HEADERS)[prefix])
 
 
 _SO = os.environ.get("VICASPLAT_HIP_LIB") or os.path.join(_HERE, "libvicasplat_hip.so")   # (override: A/B runs of two builds)
@@ -62,8 +67,8 @@ def header_constants(path: str, prefix: str) -> dict:
     return consts
 
 
-# every integer constant of every public header, under the header's own name: VS_BUF_*, VS_RASTER_*, VS_SSIM_*, VSP_*, VSV_*, VSO_*, VSJ_*, VSG_*
-for _prefix, _ in ALL_HEADERS:
+# every integer constant of every public header, under the header's own name: VS_BUF_*, VS_RASTER_*, VS_SSIM_*, VSP_*, VSV_*, VSO_*, VSJ_*, VSG_*, VSE_*
+for _prefix, _ in BOUND_HEADERS:
     globals().update(header_constants(header_path(_prefix), _prefix.upper()))
 
 AllocFn = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_int32, C.c_size_t)
@@ -99,7 +104,7 @@ def build(force: bool = False) -> str:
     src_dir = os.path.join(_HERE, "csrc")
     newest = max(os.path.getmtime(os.path.join(src_dir, f)) for f in os.listdir(src_dir)
                  if f.endswith((".hip", ".h", "Makefile")))
-    newest = max(newest, *(os.path.getmtime(header_path(prefix)) for prefix, _ in ALL_HEADERS))
+    newest = max(newest, *(os.path.getmtime(header_path(prefix)) for prefix, _ in BOUND_HEADERS))
     if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < newest:
         subprocess.check_call(["make", "-C", src_dir, "-j8"], stdout=subprocess.DEVNULL)
     return _SO
@@ -117,7 +122,7 @@ def parse_header(text: str, prefix: str = "vs_") -> dict:
     below, raises with the prototype's text (ctypes' default conversion would truncate or shift the arguments silently)."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*|^\s*#[^\n]*", "", text, flags=re.S | re.M)
     text = re.sub(r'extern\s+"C"\s*\{|\b(?:typedef\s+struct|enum)\b[^{;]*\{[^}]*\}[^;]*;|\btypedef\b[^;{]*;', "", text)
-    header = dict(ALL_HEADERS).get(prefix, f"header of the {prefix} entries")
+    header = dict(BOUND_HEADERS).get(prefix, f"header of the {prefix} entries")
     sigs = {}
     for proto in (" ".join(p.split()) for p in text.split(";")):
         if proto in ("", "}"):
@@ -159,7 +164,7 @@ def _load() -> C.CDLL:
             if L.vs_abi_version() != ABI_VERSION:     # the ctypes mirrors of the structs above are for exactly this layout
                 raise RuntimeError(f"{_SO} has ABI version {L.vs_abi_version()}, this package needs {ABI_VERSION}: rebuild it (python -c 'import __graft_entry__ as g; g.build()')")
             sigs = {}
-            for prefix, _ in ALL_HEADERS:
+            for prefix, _ in BOUND_HEADERS:
                 with open(header_path(prefix)) as f:
                     sigs.update(parse_header(f.read(), prefix=prefix))
             for name, (restype, argtypes, takes_stream) in sigs.items():

@@ -25,6 +25,8 @@ scripts do around the encoder/decoder:
   * `camera_eval_metrics` — src/evaluation/metrics.py:148-265 (ATE, RPE-trans, RPE-rot: evo's ape / rpe restated, UNVERIFIED against evo) on
     csrc/trajectory.hip, batched over scenes, device tensors out
   * `test_step` — ModelWrapper.test_step, src/model/model_wrapper.py:323-381: the six numbers it logs, per scene, batched
+  * `save_test_outputs` — the file output of ModelWrapper.test_step, model_wrapper.py:386-407: context frames, transforms.json and the rendered
+    targets beside their depth maps as PNG files made on the device (misc/image_io.py, csrc/png.hip), one encoder call per frame shape
   * `pose_eval_step` — PoseEvaluator.test_step, src/evaluation/pose_evaluator.py:77-174: the pose metrics before and after refinement
   * `render_video_wobble_step`, `render_video_interpolation_exaggerated_step`, `camera_trajectory_plot` — model_wrapper.py:685-707, 733-773 and
     the stated substitute for the plotly camera figure of :668-679, on csrc/draw.hip (visualization/drawing, camera_trajectory/wobble.py)
@@ -1125,6 +1127,38 @@ def test_step(encoder, decoder, batch: dict, *, lpips_net: LpipsVgg | None = Non
         ate, rpe_trans, rpe_rot, valid = camera_eval_metrics(model_outs["gaussian_camera_extrins"], ctx["extrinsics"], return_valid=True)
         scores.update({"ate_ours": ate, "rpe-trans_ours": rpe_trans, "rpe-rot_ours": rpe_rot, "pose_valid": valid})
     return scores
+
+
+def save_test_outputs(batch: dict, model_outs: dict, output, path, *, save_image: bool = True) -> list[Path]:
+    """The files ModelWrapper.test_step writes for a scene (model_wrapper.py:386-407), for every scene of the batch (the reference asserts
+    b == 1), under `path` (the reference's test_cfg.output_path / name):
+      <scene>/context/<index:0>6>.png   every context frame, image * 0.5 + 0.5 -- always
+      <scene>/transforms.json           export_transforms of model_outs["gaussian_camera_extrins"] with those file names -- always
+      <scene>/color/<index:0>6>.png     with save_image (test_cfg.save_image): hcat(color, vis_depth_map(depth)) of every rendered target,
+                                        the depth range taken per scene as the reference takes it
+    batch: {"scene": [B names], "context": {"image" [B,V,3,H,W] in [-1,1], "index" [B,V]}, "target": {"index" [B,Vt]}};
+    output: the decoder's, .color [B,Vt,3,H,W] and .depth [B,Vt,H,W].  All frames of one shape go through ONE encode_png_batch call: the
+    pixels never cross to the host, the files do.  save_compare (it needs a font) and save_video are not built.  Returns the image paths."""
+    from .misc import image_io
+    from .misc.utils import vis_depth_map
+    path = Path(path)
+    scenes = list(batch["scene"])
+    ctx_index = torch.as_tensor(batch["context"]["index"]).tolist()
+    names = [[f"context/{index:0>6}.png" for index in row] for row in ctx_index]
+    frames = batch["context"]["image"].detach() * 0.5 + 0.5
+    paths = [path / scene / name for scene, row in zip(scenes, names) for name in row]
+    image_io.save_images(frames.flatten(0, 1), paths)
+    for b, scene in enumerate(scenes):
+        export_transforms(model_outs["gaussian_camera_extrins"][b], path / scene / "transforms.json", file_names=names[b])
+    if save_image:
+        color = output.color.detach().float()
+        depth = torch.stack([vis_depth_map(output.depth[b]) for b in range(len(scenes))]).to(color.dtype)
+        gap = color.new_ones(color.shape[:-1] + (8,))          # layout.hcat's white gap of 8 columns between images of one height
+        tgt_index = torch.as_tensor(batch["target"]["index"]).tolist()
+        tgt_paths = [path / scene / f"color/{index:0>6}.png" for scene, row in zip(scenes, tgt_index) for index in row]
+        image_io.save_images(torch.cat([color, gap, depth], dim=-1).flatten(0, 1), tgt_paths)
+        paths += tgt_paths
+    return paths
 
 
 def pose_eval_step(encoder, decoder, batch: dict, *, steps: int = 0, rot_lr: float = 0.005, trans_lr: float = 0.005, mse_weight: float = 1.0,
